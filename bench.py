@@ -1,7 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the DiffGFDN hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling auto|weak|strong] [--epoch]
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--scaling auto|weak|strong] [--epoch]
+
+A plain run does only what the headline figure needs: it builds the workload, warms up, times EXACTLY ``--steps`` steps in one
+region, writes the outputs of the last timed step if ``--dump-outputs DIR`` is given (``DIR/<name>.npy``: every loss term the
+step returns, the flat gradient and every parameter after the step's Adam update; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array) and prints the JSON line.  Everything else described below -- the repeated
+timed regions (``--repeats``, default 5 there), the roofline leg, the CPU baseline with ``loss_delta_vs_cpu``, the N = 32 /
+reference-recipe / directional sub-records, at N > 1 the weak-scaling and band-sharded figures, the figures read from
+profiles/ -- is measured only with ``--full``.
 
 With N > 1 and no launcher around it (WORLD_SIZE unset) the script starts its own N ranks -- a child
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`` -- BEFORE anything touches
@@ -23,10 +31,10 @@ STRONG scaling -- the reference's global batch of 32 per band split over the ran
 steps its own 32 receivers per band, global batch 32 N) and the band-sharded placement (whole bands over the ranks, no
 collective) beside it in ``extra``; ``--scaling weak`` / ``strong``: that one figure only.  Either way the gradients of all
 bands and the per-band loss terms are summed by ONE all-reduce of one flat buffer, between the step's two graphs (or inside
-one graph with ``--captured-allreduce``).  At N = 1 the default line also carries the N = 32 configuration and the
+one graph with ``--captured-allreduce``).  At N = 1 the ``--full`` line also carries the N = 32 configuration and the
 directional configuration as short sub-records (``extra.n32``, ``extra.directional``).
 
-The JSON line also carries
+With ``--full`` the JSON line also carries
   roofline     : HBM roofline of the dominant kernel.  ``achieved`` uses its duration IN THE STEP: the same launch
                  sequence on the same streams as the timed graph (host launches), bracketed by HIP events on the
                  stream the kernel is launched on; the duration of the kernel alone on the chip is reported beside it
@@ -110,6 +118,51 @@ ROOFLINE_EAGER_STEPS = 20
 CPU_BASELINE_THREADS = 16            # the torch CPU path anti-scales beyond this on the 2x64-core host
 PROFILE_TAG = 'r06'
 REFERENCE_EPOCH_S_PER_BAND = 139.1   # reference trainer, N = 16, 8 vCPU, one band, one epoch
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def collect_outputs(prefix, obj, into):
+    """Flattens what a step returned (tensors, numbers, dicts / lists of them) into ``into``: {name: host numpy array}, float64
+    where the value is float64 / complex128, float32 otherwise (complex values as (..., 2) real pairs).  Copies: the step's
+    loss tensors are static buffers that later launches overwrite."""
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            collect_outputs(f'{prefix}_{k}'.replace('__', '_').strip('_'), v, into)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            collect_outputs(f'{prefix}_{i}', v, into)
+    elif torch.is_tensor(obj):
+        t = obj.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        into[prefix] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy().copy()
+    elif isinstance(obj, (int, float, np.floating, np.integer)):
+        into[prefix] = np.asarray(float(obj), dtype=np.float64)
+
+
+def collect_model(net, optimizer, into, tag=''):
+    """The parameters as the step's update left them (param_<tag><name>) and the flat gradient buffer that update consumed"""
+    for name, p in net.named_parameters():
+        collect_outputs(f'param_{tag}{name}'.replace('.', '_'), p, into)
+    flat = getattr(optimizer, 'flat_grad', None)
+    if torch.is_tensor(flat):
+        collect_outputs(f'grad_{tag}flat', flat, into)
+
+
+def dump_outputs(directory, arrays):
+    """``directory``/<name>.npy for every array; at most DUMP_BUDGET_BYTES in all: when the arrays are larger, every array above
+    its equal share of the budget is cut to a fixed sample (sorted flat indices from RandomState(0): the same in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+        for name, a in list(arrays.items()):
+            if a.nbytes > share:
+                keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[name] = a.reshape(-1)[keep]
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def host_cpu_model():
@@ -648,15 +701,24 @@ def run_directional(args, device, rank, world):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # roofline leg: the backward kernel of the directional EDC loss (the largest HBM-bound launch of the band-step since the
-    # transforms run on the 27 line responses), in the step
-    tr, step, store = steps[0]
-    lines = tr._use_lines(step.batch)
-    hip_ops.kernel_timer.watch = 'k_em_bwd' if lines else 'irfft_pow2_fwd'
-    hip_ops.kernel_timer.start()
-    for _ in range(10):
-        tr.train_step(step.batch)
-    kt = hip_ops.kernel_timer.stop()
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        collect_outputs('loss_total', total, arrays)
+        collect_outputs('loss', parts, arrays)
+        for q, (tr_q, _, _) in enumerate(steps):
+            collect_model(tr_q.net, getattr(tr_q, 'optimizer', None), arrays, tag=f'band{q}_')
+        dump_outputs(args.dump_outputs, arrays)
+    kt, lines = None, False
+    if args.full:
+        # roofline leg: the backward kernel of the directional EDC loss (the largest HBM-bound launch of the band-step since the
+        # transforms run on the 27 line responses), in the step
+        tr, step, store = steps[0]
+        lines = tr._use_lines(step.batch)
+        hip_ops.kernel_timer.watch = 'k_em_bwd' if lines else 'irfft_pow2_fwd'
+        hip_ops.kernel_timer.start()
+        for _ in range(10):
+            tr.train_step(step.batch)
+        kt = hip_ops.kernel_timer.stop()
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -703,7 +765,7 @@ def run_directional(args, device, rank, world):
                                      'register-resident 256 x 256 passes)',
                            'avg_launch_us': us, 'launches': kt['launches'], 'alg_bytes_per_unit': per,
                            'units_per_launch': units, 'measured': 'HIP events around both passes in 10 host-launched steps'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline_directional(steps[0][0], z, Gd, L, J)
     return out
 
@@ -786,9 +848,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=5,
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline figure: repeated timed regions, roofline leg, CPU baseline and loss / gradient '
+                         'deltas against it, the N = 32 / reference-recipe / directional sub-records, at N > 1 the weak-scaling '
+                         'and band-sharded figures (off by default: a plain run times --steps steps and prints its line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (loss terms, flat gradient, the '
+                         'parameters after its Adam update) as DIR/<name>.npy, float32 / float64, at most 64 MB in all')
+    ap.add_argument('--repeats', type=int, default=None,
                     help='timed regions of --steps steps each (N = 1; ms_per_step is the MEDIAN region, the spread is in '
-                         'extra.repeat_spread): a 20-step region of this workload is an 8 ms sample')
+                         'extra.repeat_spread): a 20-step region of this workload is an 8 ms sample.  Default: 1, so that '
+                         '--steps is the number of timed steps; 5 with --full')
     ap.add_argument('--scaling', choices=('auto', 'weak', 'strong'), default='auto',
                     help='auto (default): N = 1 the step at batch 32; N > 1 the headline is STRONG scaling (the reference\'s '
                          'global batch of 32 per band split over the ranks) with the weak figure (32 receivers per band per '
@@ -799,7 +869,7 @@ def main():
                     help='time whole epochs (19 train + 5 validation steps + checkpoints); --steps = epochs timed')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the N = 32 and directional sub-records of the default N = 1 line')
+                    help='skip the N = 32 and directional sub-records of the N = 1 line (--full)')
     ap.add_argument('--extra-steps', type=int, default=40, help='timed steps of each sub-record')
     ap.add_argument('--dir-bank', type=int, default=1,
                     help='directional config: 1 (default) = trainer.DirectionalBank, ONE graph steps all bands; 0 = one graph '
@@ -836,6 +906,8 @@ def main():
     ap.add_argument('--bands', type=int, default=None,
                     help='octave bands stepped together (1 = BASELINE.json configs[1], the 500 Hz band alone)')
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.recipe == 'reference':
         globals().update(RECIPE='reference', G=3, BAND_CENTRES=REFERENCE_RECIPE_CENTRES)
     if args.bands is None:
@@ -1099,6 +1171,11 @@ def run_omni(args, device, rank, world, ranks_seen, rank_devices, sub_record=Fal
                                         'band after another (wav export skipped)',
                       'speedup_vs_reference_epoch': REFERENCE_EPOCH_S_PER_BAND * nbands / (elapsed / len(ep))}
         total, ktimes, iso = torch.tensor(trainer.train_loss)[:, -1], {}, {}
+        if args.dump_outputs and rank == 0:
+            arrays = {}
+            collect_outputs('loss_total', total, arrays)
+            collect_model(trainer.net, trainer.optimizer, arrays)
+            dump_outputs(args.dump_outputs, arrays)
         value = rirs_per_s * FRAMES
         scaling = 'strong'               # (an epoch is a fixed amount of work whatever the number of ranks)
     else:
@@ -1126,12 +1203,18 @@ def run_omni(args, device, rank, world, ranks_seen, rank_devices, sub_record=Fal
         if spread.get('regions', 1) > 1:
             extra['repeat_spread'] = spread
         total = parts['_total']
+        if args.dump_outputs and rank == 0 and not sub_record:
+            arrays = {}
+            collect_outputs('loss', parts, arrays)
+            collect_model(trainer.net, trainer.optimizer, arrays)
+            dump_outputs(args.dump_outputs, arrays)
 
-        # roofline leg (rank 0): the SAME launch sequence on the same streams, launched from the host so that the
+        # roofline leg (rank 0, --full): the SAME launch sequence on the same streams, launched from the host so that the
         # dominant kernel can be bracketed by HIP events on its stream -- its duration in the step, beside its
         # duration alone on the chip
         ktimes, iso, kpair, iso_pair = {}, {}, {}, {}
-        if rank == 0 and use_bank and world == 1 and getattr(trainer, '_fused', None) is not None and not sub_record:
+        if rank == 0 and use_bank and world == 1 and getattr(trainer, '_fused', None) is not None and not sub_record \
+                and args.full:
             hip_ops.kernel_timer.watch = PAIR_KERNELS
             hip_ops.kernel_timer.start()
             for _ in range(ROOFLINE_EAGER_STEPS):
@@ -1159,7 +1242,7 @@ def run_omni(args, device, rank, world, ranks_seen, rank_devices, sub_record=Fal
         rirs_per_s = nbands * b_local * world * args.steps / elapsed
         value = rirs_per_s * FRAMES
 
-        if world > 1 and use_bank and args.scaling == 'auto':
+        if world > 1 and use_bank and args.scaling == 'auto' and args.full:
             # ---- beside the strong-scaling headline: weak scaling (32 receivers per band per RANK, global batch 32 N) on
             # the same models and data, and the band-sharded placement (no collective)
             wstep = trainer.graphed(data, BATCH)
@@ -1266,17 +1349,17 @@ def run_omni(args, device, rank, world, ranks_seen, rank_devices, sub_record=Fal
         # the PMC traffic of the replayed step's launches (profiles/<tag>_step_traffic.json, tools/make_profiles.py)
         out['linear_alg_bytes_per_rir'] = LINEAR_ALG_BYTES_PER_RIR
         out['linear_alg_hbm_frac'] = rirs_per_s / world * LINEAR_ALG_BYTES_PER_RIR / 1e9 / HBM_PEAK_GBS
-        st = step_traffic()
+        st = step_traffic() if args.full else None
         if st is not None and use_bank and nbands == len(BAND_CENTRES) and NPER == 4 and not sub_record:
             out['step_traffic_bytes'] = st['bytes_per_step']
             out['step_traffic_frac'] = st['bytes_per_step'] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
             out['step_traffic_source'] = st['source']
-        if world == 1 and not args.no_cpu_baseline and not sub_record:
+        if world == 1 and args.full and not args.no_cpu_baseline and not sub_record:
             out['cpu_baseline'] = cpu_baseline(room, delays, filt.cpu().numpy().astype(np.complex128), device=device,
                                                steps=args.cpu_steps)
     # ---- the other two BASELINE.json configurations on the same clock (N = 1, default run): short sub-records
-    if world == 1 and not sub_record and not args.no_extras and not args.epoch and use_bank and nbands == len(BAND_CENTRES) \
-            and NPER == 4 and RECIPE is None:
+    if world == 1 and not sub_record and args.full and not args.no_extras and not args.epoch and use_bank \
+            and nbands == len(BAND_CENTRES) and NPER == 4 and RECIPE is None:
         del step, trainer, data, net
         torch.cuda.empty_cache()
         out.setdefault('extra', {})
@@ -1289,12 +1372,12 @@ def run_omni(args, device, rank, world, ranks_seen, rank_devices, sub_record=Fal
 
 
 def sub_bench(args, device, which):
-    """BASELINE.json configs[4] (N = 32 = 4 x 8 lines) / configs[3] (directional) as short sub-records of the default line, so
-    that the driver's clock covers them too: ``--extra-steps`` timed steps after 5 warm-up steps, no roofline / CPU legs
-    (those are in ``bench.py --lines-per-group 8`` / ``--config directional``)."""
+    """BASELINE.json configs[4] (N = 32 = 4 x 8 lines) / configs[3] (directional) as short sub-records of the ``--full`` line, so
+    that one clock covers them too: ``--extra-steps`` timed steps after 5 warm-up steps, no roofline / CPU legs
+    (those are in ``bench.py --full --lines-per-group 8`` / ``--full --config directional``)."""
     import copy
     a = copy.copy(args)
-    a.steps, a.warmup, a.no_cpu_baseline = args.extra_steps, 5, True
+    a.steps, a.warmup, a.no_cpu_baseline, a.dump_outputs = args.extra_steps, 5, True, None
     t0 = time.perf_counter()
     if which == 'n32':
         globals()['NPER'] = 8

@@ -108,14 +108,14 @@ on).  Rebuilt by `python tools/make_profiles.py {tag}`.  The `r01_*` ... `r05_*`
 
 | file | command | what it holds |
 |---|---|---|
-| `{tag}_bench_n1.json` | `python bench.py` | the bench JSON line (graph-replay steps, roofline leg, CPU baseline with `loss_delta_vs_cpu`) |
-| `{tag}_bench_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline` | per-kernel totals / averages (includes the one-off dataset front end, the 20 host-launched roofline steps and the 60 isolated launches of the roofline kernel) |
+| `{tag}_bench_n1.json` | `python bench.py --full` | the bench JSON line (graph-replay steps, roofline leg, CPU baseline with `loss_delta_vs_cpu`) |
+| `{tag}_bench_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu-baseline` | per-kernel totals / averages (includes the one-off dataset front end, the 20 host-launched roofline steps and the 60 isolated launches of the roofline kernel) |
 | `{tag}_pmc_hbm_bytes.csv` | `rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline --eager`, and the same with `--pmc WRITE_SIZE` (separate passes) | average FETCH_SIZE / WRITE_SIZE per launch of every hand-written kernel, by grid size; read bytes corrected x2 for gfx950 as MI355X_MICROARCH.md prescribes |
 | `{tag}_graph_step_timeline.txt` | from the kernel trace of the stats run | every kernel of one replayed step with start/end and hardware queue |
 | `{tag}_step_kernel_durations.csv` | from the kernel trace of the stats run | per kernel: launches per step, average duration and microseconds per step over 100 consecutive REPLAYED steps only (what `roofline.top` of the bench line is built from) |
-| `{tag}_directional_bench.json`, `{tag}_directional_kernels.txt`, `{tag}_directional_pmc_hbm_bytes.csv` | `bash tools/run_dir_measurements.sh {tag}` (its own gpurun call) + `python tools/make_dir_profiles.py {tag}` | BASELINE.json configs[3]: the bench line of `python bench.py --config directional` (roofline block of `k_em_bwd` with PMC traffic, CPU baseline with loss and gradient deviations), kernel totals of the graph-replayed band-steps, PMC bytes per launch of its kernels |
+| `{tag}_directional_bench.json`, `{tag}_directional_kernels.txt`, `{tag}_directional_pmc_hbm_bytes.csv` | `bash tools/run_dir_measurements.sh {tag}` (a GPU session of its own) + `python tools/make_dir_profiles.py {tag}` | BASELINE.json configs[3]: the bench line of `python bench.py --full --config directional` (roofline block of `k_em_bwd` with PMC traffic, CPU baseline with loss and gradient deviations), kernel totals of the graph-replayed band-steps, PMC bytes per launch of its kernels |
 | `{tag}_n32_kernels.txt`, `{tag}_n32_timeline.txt` | `bash tools/run_aux.sh {tag}` (`tools/run_n32_profile.sh` + `tools/timeline.py`; its own gpurun call) | kernel totals and one replayed step of the 7-band step at N = 32 (configs[4]) |
-| `{tag}_recipe_bench.json`, `{tag}_recipe_timeline.txt` | `bash tools/run_aux.sh {tag}` | `bench.py --recipe reference`: the sub-band driver's own configuration (8 bands, N = 12, per-band gain networks) in one bank: bench line and one replayed step |
+| `{tag}_recipe_bench.json`, `{tag}_recipe_timeline.txt` | `bash tools/run_aux.sh {tag}` | `bench.py --full --recipe reference`: the sub-band driver's own configuration (8 bands, N = 12, per-band gain networks) in one bank: bench line and one replayed step |
 | `{tag}_step_traffic.json` | this script | the PMC traffic of ALL launches of one replayed step (`step_traffic_bytes` of the bench line) |
 | `r06_edc_band_experiment.txt` | several gpurun calls of round 6 (`tools/run_ab.sh`, `run_probe.sh`, wall-clock stamps from a probe build) | measured negatives of round 6: the EDC term with the band's receivers inside the workgroup, the gain network on a lane of its own, the side stream's tail reordered (DESIGN.md section 4.3) |
 | `r06_parity_margins.txt` | one full `pytest -m gpu` run; `tests/margins.py` | how far inside its bound every tolerance check of the GPU suite lands (worst value per test and check): the evidence behind the tightened gradient bounds (DESIGN.md section 2) |

@@ -373,6 +373,7 @@ struct BluArgs {
   float* edge;          // rader: per-(item, column block) partial sums for the t = 0 / k = 0 terms
   int nedge;            // rader: partials per item
   int batch;
+  int xpad;             // col128 / row512 passes: the grid covers batch rounded up to 8 items (xcd_item_map)
   int pair;             // slot mode only: items 2b, 2b+1 share one transform; time signals pair-interleaved (float2)
   int items;            // number of items (rows of the spectrum side)
   int slot;             // Rader + col128: the SPECTRUM side is in slot order (gfdn_irfft_odd_slot_order): no gather / scatter
@@ -400,10 +401,11 @@ extern __shared__ float2 dyn_lds[];
 // in ONE L2 across the three kernels: the Rader gather / scatter and the transposed work-block
 // accesses then hit L2 instead of over-fetching from HBM (PMC: 62 MB fetched vs 17 MB compulsory
 // before).  Placement only affects speed, never correctness; any batch not a multiple of 8 uses the
-// plain map.
-__device__ __forceinline__ void xcd_item_map(int ntiles, int batch, int& tile, int& b) {
+// plain map, unless the launch's grid was padded to the next multiple of 8 items (`pad`, blu_xpad): the
+// blocks of the items past the batch then return false and leave at once.
+__device__ __forceinline__ bool xcd_item_map(int ntiles, int batch, int& tile, int& b, int pad = 0) {
   const int id = blockIdx.x;
-  if ((batch & 7) == 0) {
+  if ((batch & 7) == 0 || pad) {
     const int j = id >> 3, q = j / ntiles;
     b = (id & 7) + 8 * q;
     tile = j - q * ntiles;
@@ -411,6 +413,16 @@ __device__ __forceinline__ void xcd_item_map(int ntiles, int batch, int& tile, i
     b = id / ntiles;
     tile = id - b * ntiles;
   }
+  return b < batch;
+}
+
+// The padded grid for a batch that is no multiple of 8 (the linear step's 14 pairs of group signals: the scatter of the
+// pair forward pass wrote every 128-byte line of a pair's output from all eight L2s).  The XCDs then hold ceil(batch / 8)
+// or one item fewer each, so the map is taken only where that imbalance stays under a quarter of the launch; batches
+// under 8 keep the plain map (they would leave XCDs empty).
+static int blu_xpad(int batch) {
+  const int padded = (batch + 7) & ~7;
+  return (batch & 7) != 0 && batch > 8 && 4 * padded <= 5 * batch;
 }
 
 
@@ -649,7 +661,7 @@ __global__ __launch_bounds__(256) void k_blu_row512(BluArgs a) {
   build_tw2(thi, tlo, L);
   __syncthreads();
   int tile, b;
-  xcd_item_map(g.L1 / 4, a.batch, tile, b);
+  if (!xcd_item_map(g.L1 / 4, a.batch, tile, b, a.xpad)) return;
   const int k1 = tile * 4 + wave;
   float2* buf = bufs + wave * ROW512_LDS;
   float2* wk = a.work + (size_t)b * L + (size_t)k1 * L2;
@@ -770,7 +782,7 @@ __global__ __launch_bounds__(256) void k_blu_col128_fwd(BluArgs a) {
   const int c = lane & 7, l = lane >> 3;
   build_tw2(thi, tlo, L);
   int tb, b;
-  xcd_item_map(L2 / 32, a.batch, tb, b);
+  if (!xcd_item_map(L2 / 32, a.batch, tb, b, a.xpad)) return;
   const int tile = tb * 4 + wave, c0 = tile * 8;
   float edge = 0.f, edge2 = 0.f;
   float2 v[16];
@@ -906,7 +918,7 @@ __global__ __launch_bounds__(256) void k_blu_col128_inv(BluArgs a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int c = lane & 7, l = lane >> 3;
   int tb, b;
-  xcd_item_map(L2 / 32, a.batch, tb, b);
+  if (!xcd_item_map(L2 / 32, a.batch, tb, b, a.xpad)) return;
   const int tile = tb * 4 + wave, c0 = tile * 8;
   const float2* wk = a.work + (size_t)b * L;
   float2 v[16];
@@ -1109,6 +1121,7 @@ static int blu_run(const void* table, int n, const void* in, int ld_in, int batc
   if ((in3 && !(tslots && in2)) || (oscale && !(slot == 2 && !adjoint))) return GFDN_E_BADARG;
   if (slot && !slot_order_ok(n)) return GFDN_E_UNSUPPORTED;
   if (a.pair) a.batch = (batch + 1) / 2;          // work blocks = item pairs
+  a.xpad = 0;                                     // set below for the kernels that take the padded grid
   a.adjoint = adjoint;
   a.in = in;
   a.in2 = adjoint ? in2 : nullptr;
@@ -1128,19 +1141,23 @@ static int blu_run(const void* table, int n, const void* in, int ld_in, int batc
   const bool col128 = g.L1 == 128 && g.L2 % 32 == 0 && tc == 8;       // wave-per-tile column kernels
   if (cmp && !(col128 && a.pair && rader)) return GFDN_E_UNSUPPORTED;
   const size_t tw2_elems = (size_t)((g.L >> TW_LOBITS) > 0 ? (g.L >> TW_LOBITS) : 1) + (1 << TW_LOBITS);
+  const bool row512 = g.L2 == 512 && g.L1 % 4 == 0;
+  // the three passes of a transform share the map or the work block changes its L2 between them
+  a.xpad = (col128 && row512 && blu_xpad(a.batch)) ? 1 : 0;
+  const int gbatch = a.xpad ? (a.batch + 7) & ~7 : a.batch;
   if (stages & 1) {
     if (col128)
-      hipLaunchKernelGGL(k_blu_col128_fwd, dim3((g.L2 / 32) * a.batch), dim3(256),
+      hipLaunchKernelGGL(k_blu_col128_fwd, dim3((g.L2 / 32) * gbatch), dim3(256),
                          (tw2_elems + 4 * CW_LDS) * sizeof(float2), s, a);
     else
       hipLaunchKernelGGL(k_blu_col_fwd, dim3((g.L2 / tc) * batch), dim3(256), lc, s, a);
     GFDN_LAUNCH_CHECK();
   }
   if (stages & 2) {
-    if (g.L2 == 512 && g.L1 % 4 == 0) {
+    if (row512) {
       const size_t lr5 = (128 + ((g.L >> TW_LOBITS) > 0 ? (g.L >> TW_LOBITS) : 1) + (1 << TW_LOBITS) +
                           4 * ROW512_LDS) * sizeof(float2);
-      hipLaunchKernelGGL(k_blu_row512, dim3((g.L1 / 4) * a.batch), dim3(256), lr5, s, a);
+      hipLaunchKernelGGL(k_blu_row512, dim3((g.L1 / 4) * gbatch), dim3(256), lr5, s, a);
     } else {
       hipLaunchKernelGGL(k_blu_row, dim3((g.L1 / tr) * batch), dim3(256), lr, s, a);
     }
@@ -1152,9 +1169,11 @@ static int blu_run(const void* table, int n, const void* in, int ld_in, int batc
       // written when too many pairs are in flight per XCD (PMC: 4.8 x the algorithmic write bytes).  Twice the
       // LDS per block caps a CU at two blocks = four pairs per XCD: 70 -> 60 us (one block per CU: 62 us;
       // non-temporal loads of the work block: no gain).  The adjoint's stores are coalesced and keep 3 blocks.
+      // (Both hold for batches that take the XCD map; the 14 pairs of group signals did not before blu_xpad and wrote
+      // 32.8 MB for 7.3: every line of a pair's output met slots from all eight L2s.  Padded: 7.2 MB, 31 -> 21 us.)
       const size_t linv = (size_t)((a.pair && !a.adjoint) ? 2 : 1) * 4 * CW_LDS * sizeof(float2);
       if ((rc = ensure_dyn_lds(k_blu_col128_inv, linv))) return rc;
-      hipLaunchKernelGGL(k_blu_col128_inv, dim3((g.L2 / 32) * a.batch), dim3(256), linv, s, a);
+      hipLaunchKernelGGL(k_blu_col128_inv, dim3((g.L2 / 32) * gbatch), dim3(256), linv, s, a);
     }
     else
       hipLaunchKernelGGL(k_blu_col_inv, dim3((g.L2 / tc) * batch), dim3(256), lc, s, a);

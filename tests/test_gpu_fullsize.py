@@ -416,7 +416,7 @@ def test_round5_step_equals_round4_step_full_size(per_band):
     """K = 65 537, two bands, one replayed step: the step with the one-launch EDC term (csrc/edcone.hip), the normalisation
     scale joining behind the transform and the fused tail / head (k_tf_tail) against the same step with the three switched
     off (round 4's launch sequence): losses to 5e-6, gradients to rounding (dL/dM: DESIGN.md section 2).  per_band = 4: the
-    wave-per-receiver gain network, with which the scale sits INSIDE the receiver gains (FusedBankStep.scale_in_gains)."""
+    wave-per-receiver gain network, with which the scale sits INSIDE the receiver gains (FusedBankStep.scale_late)."""
     from diffgfdn_amd.bandbank import BandBank, BandBankTrainer, BandStackedDataset
     res = {}
     sel0, sel1 = ([[0, 3], [1, 4]], [[2, 5], [0, 3]]) if per_band == 2 else ([[0, 3, 1, 5], [1, 4, 2, 0]], [[2, 5, 0, 4], [0, 3, 5, 1]])

@@ -300,7 +300,7 @@ def test_merge_into_slot_order(ops):
 
 def test_gain_network_backward_with_the_scale_in_the_gains(ops):
     """mlp_gains_bwd(ggains_parts, colscale) on rows of dL/d(gains s) == the backward on the rows times s
-    (bankstep.FusedBankStep.scale_in_gains)."""
+    (bankstep.FusedBankStep.scale_late)."""
     from diffgfdn_amd import _lib
     nb, Bper, G, F, H, nh, chunks = 3, 8, 4, 20, 16, 2, 37
     B = nb * Bper

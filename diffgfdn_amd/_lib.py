@@ -21,6 +21,8 @@ SIGNATURES = {
     "gfdn_zprep": (c_int, [_P, c_int, _P, _P, _P]),
     "gfdn_ortho_fwd": (c_int, [_P, c_int, c_int, _P, _P, _P]),
     "gfdn_ortho_bwd": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "gfdn_coupled_feedback_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "gfdn_coupled_feedback_bwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "gfdn_solve_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P]),
     "gfdn_solve_bwd_work_bytes": (c_size_t, [c_int, c_int]),
     "gfdn_solve_bwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),

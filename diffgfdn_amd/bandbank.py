@@ -21,9 +21,14 @@ and the post-Adam state of every band against single-band steps and the CPU orac
 ``nn.Module`` stays alive: its parameters are views into the bank's stacked tensors, so
 ``nets[i].state_dict()`` is the reference-shaped checkpoint of band i at any time.
 
-Supported layout (the reference's sub-band recipe, run_subband_training_treble.py:105-154): SCALAR
-coupling with zero inter-group coupling, fixed common decay times, MLP output gains.  Other layouts
-train band by band with ``subband.train_bands``.
+Supported layout (the reference's sub-band recipes, run_subband_training_treble.py:105-154): SCALAR
+coupling, fixed common decay times, MLP output gains -- with zero inter-group coupling (the default
+recipe) or with learnable coupling angles in every band (``--allow_coupling``, :143-146).  A coupled
+bank has one more stacked leaf, ``feedback_loop_alpha`` (bands, G (G - 1) / 2); one launch builds every
+band's dense A = block_M o kron(Phi(alpha), 1) (csrc/coupling.hip) and the per-bin elimination takes
+the bands as ``bands`` blocks of N lines.  It steps under autograd: the explicit launch sequence of
+bankstep.py assumes a block-diagonal feedback matrix.  Other layouts (RANDOM or FILTER coupling,
+absorption filters, learnable decay times) train band by band with ``subband.train_bands``.
 """
 import contextlib
 import os
@@ -37,8 +42,8 @@ from torch import nn
 
 from . import hip_ops as ops
 from .config import CouplingMatrixType, TrainerConfig
-from .functional import (ColorlessTerms, FrequencyGrid, MlpGains, OrthoParam, OutputStage, ResolventSolve,
-                         SubFdnColorless)
+from .functional import (ColorlessTerms, CoupledFeedback, FrequencyGrid, MlpGains, OrthoParam, OutputStage,
+                         ResolventSolve, SubFdnColorless)
 from .bankstep import FusedBankStep
 from .losses import decay_losses, edc_loss, shard_loss_scales
 from .optim import FlatAdam
@@ -51,6 +56,7 @@ class BandBank(nn.Module):
         input_gains, output_gains (bands, N);  feedback_loop_M (bands, G, n, n);
         output_scalars_w (bands, P) -- every band's MLP parameters packed in named_parameters() order (bands whose networks
         differ in size: ONE vector, band after band).
+        feedback_loop_alpha (bands, G (G - 1) / 2) -- the coupling angles; a coupled bank only.
     The names keep the substrings the reference selects learning-rate groups by
     (trainer.py:157-216: 'input_gains', 'output_gains', 'output_scalars' -> io_lr, the rest -> lr)."""
 
@@ -65,9 +71,11 @@ class BandBank(nn.Module):
             fl = net.feedback_loop
             if (net.num_groups, net.num_delay_lines_per_group) != (G, n):
                 raise ValueError("BandBank: bands must have the same groups x delay lines per group")
-            if not fl.uncoupled:
-                raise NotImplementedError("BandBank: zero inter-group coupling only (train other layouts "
+            if fl.coupling_matrix_type in (CouplingMatrixType.RANDOM, CouplingMatrixType.FILTER):
+                raise NotImplementedError("BandBank: SCALAR coupling only, zero or learnable angles (train other layouts "
                                           "band by band with subband.train_bands)")
+            if fl.uncoupled != n0.feedback_loop.uncoupled:
+                raise ValueError("BandBank: every band coupled or every band with zero coupling, not a mix")
             if fl.use_absorption_filters:
                 raise NotImplementedError("BandBank: scalar absorption gains (the sub-band recipe)")
             if fl.learn_decay_times or not isinstance(fl.M, nn.Parameter):
@@ -84,6 +92,9 @@ class BandBank(nn.Module):
         self.num_delay_lines = G * n
         self.sample_rate = n0.sample_rate
         self.use_colorless_loss = all(net.use_colorless_loss for net in nets)
+        # learnable inter-group coupling (run_subband_training_treble.py:143-146, --allow_coupling): every band's feedback
+        # matrix is the dense A = block_M o kron(Phi(alpha), 1) instead of blockdiag(Q_g Q_g)
+        self.coupled = not n0.feedback_loop.uncoupled
         N = G * n
         # every band's gain network: (neurons per layer, hidden layers).  The reference's sub-band driver sizes them per band
         # (run_subband_training_treble.py:61-73: 1 x 8, 1 x 16, 5 x 16, 3 x 128); features and output limits are shared
@@ -107,6 +118,9 @@ class BandBank(nn.Module):
             self.input_gains = nn.Parameter(torch.stack([net.input_gains.detach().reshape(N) for net in nets]))
             self.output_gains = nn.Parameter(torch.stack([net.output_gains.detach().reshape(N) for net in nets]))
             self.feedback_loop_M = nn.Parameter(torch.stack([net.feedback_loop.M.detach() for net in nets]))
+            if self.coupled:
+                self.feedback_loop_alpha = nn.Parameter(torch.stack(
+                    [net.feedback_loop.alpha.detach().reshape(G * (G - 1) // 2) for net in nets]))
             packed = [torch.cat([p.detach().reshape(-1) for p in ps]) for ps in self._mlp_params]
             # equal networks: (bands, P); mixed: the bands' packed sets one after the other in ONE vector
             self.output_scalars_w = nn.Parameter(torch.cat(packed) if self.mixed_networks else torch.stack(packed))
@@ -135,6 +149,8 @@ class BandBank(nn.Module):
             net.input_gains.data = self.input_gains.data[i].view(N, 1)
             net.output_gains.data = self.output_gains.data[i].view(N, 1)
             net.feedback_loop.M.data = self.feedback_loop_M.data[i]
+            if self.coupled:
+                net.feedback_loop.alpha.data = self.feedback_loop_alpha.data[i]
             off = self._w_off[i]
             wflat = self.output_scalars_w.data.view(-1)
             for p in self._mlp_params[i]:
@@ -173,10 +189,22 @@ class BandBank(nn.Module):
         return OutputStage.apply(Ysub, self.output_gains.view(-1), self._eye,
                                  self.num_delay_lines_per_group, None, None, None, self.num_bands)
 
-    def delay_line_responses(self, z: torch.Tensor, QQ: torch.Tensor) -> torch.Tensor:
-        """Y (K, bands*N): y = (D Gamma^-1 - blockdiag(Q_g Q_g))^-1 b for every band."""
-        return ResolventSolve.apply(QQ, self.inv_gamma, self.input_gains.view(-1), FrequencyGrid.of(z),
-                                    self.delays, False)
+    def delay_line_responses(self, z: torch.Tensor, QQ: torch.Tensor, Q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Y (K, bands*N): y = (D Gamma^-1 - blockdiag(Q_g Q_g))^-1 b for every band; a coupled bank (``Q``: the
+        rotations) solves against every band's dense A = block_M o kron(Phi, 1) instead: one launch builds all of them,
+        and the per-bin elimination takes the bands as ``bands`` blocks of N lines."""
+        if not self.coupled:
+            return ResolventSolve.apply(QQ, self.inv_gamma, self.input_gains.view(-1), FrequencyGrid.of(z),
+                                        self.delays, False)
+        N = self.num_delay_lines
+        A, Phi = CoupledFeedback.apply(Q, self.feedback_loop_alpha, self.num_groups, self.num_delay_lines_per_group,
+                                       self.num_bands)
+        # what get_param_dict() of a band reports as its coupling matrix between two forwards (feedback_loop.py:406-411)
+        self.coupling_matrices = Phi
+        for q, net in enumerate(self.nets):
+            net.feedback_loop.phi = Phi[q]
+        return ResolventSolve.apply(A.view(self.num_bands, N, N), self.inv_gamma, self.input_gains.view(-1),
+                                    FrequencyGrid.of(z), self.delays, False)
 
     def group_gains(self, positions: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
         """(bands*B, G) receiver gains; item i encodes positions[rows[i]] with band i // B's network."""
@@ -444,8 +472,12 @@ class BandBankTrainer:
         # (the gain network last: its range of the flat buffers can then be stepped on its own, bankstep.py)
         groups = [{'params': [bank.output_gains], 'lr': cfg.io_lr},
                   {'params': [bank.input_gains], 'lr': cfg.io_lr},
-                  {'params': [bank.feedback_loop_M], 'lr': cfg.lr},
-                  {'params': [bank.output_scalars_w], 'lr': cfg.io_lr}]
+                  {'params': [bank.feedback_loop_M], 'lr': cfg.lr}]
+        if bank.coupled and bank.feedback_loop_alpha.numel():
+            # the coupling angles at their own rate (init_scheduler :152-228: 'feedback_loop.alpha' -> coupling_angle_lr);
+            # only a coupled bank has the group, so a zero-coupling bank's flat buffers keep their layout
+            groups.append({'params': [bank.feedback_loop_alpha], 'lr': cfg.coupling_angle_lr})
+        groups.append({'params': [bank.output_scalars_w], 'lr': cfg.io_lr})
         # (3 loss slots per band ride the gradient bucket of a data-parallel job: EDR, EDC, colorless share)
         self.optimizer = BandFlatAdam(groups, self.num_bands, extra_slots=3 * self.num_bands)
         bank.relink()                               # the leaves now live in the flat buffer
@@ -477,7 +509,9 @@ class BandBankTrainer:
             warnings.warn("BandBankTrainer: this layout (more than 8 lines per group -- more than 4 off the unit circle --, "
                           "more than 4 groups per band or more than 64 blocks in the bank) is outside the explicit "
                           "block-transfer-function step; the bank "
-                          "steps through the per-bin elimination kernels under autograd (same results, slower)",
+                          "steps through the per-bin elimination kernels under autograd (same results, slower)"
+                          + (".  Learnable inter-group coupling is such a layout: the explicit step assumes a "
+                             "block-diagonal feedback matrix" if bank.coupled else ""),
                           RuntimeWarning, stacklevel=2)
         # leaves are first touched on one stream and receive gradients from the other by design (§5.1): the
         # engine synchronises them; its per-backward warning about that would only hide real messages
@@ -638,6 +672,8 @@ class BandBankTrainer:
         if fused and side is not None:
             main.wait_event(rot_done)
             QQ.record_stream(main)
+            if bank.coupled:
+                Q.record_stream(main)                  # (the coupled matrices are built from Q on the main stream)
         elif fused:
             rgain = bank.group_gains(data['norm_listener_position'], rows)
         else:
@@ -645,6 +681,8 @@ class BandBankTrainer:
             if side is not None:
                 main.wait_event(ready)
                 QQ.record_stream(main)
+                if bank.coupled:
+                    Q.record_stream(main)
         K = z.shape[-1]
         Ku = (K + 1) // 2 if K % 2 == 1 else K          # irfft(X, n = K) reads bins 0..(K-1)/2 only
         # Slot order (n = 65 537): the irfft's natural input order is a fixed permutation of the bins, some of them
@@ -656,7 +694,7 @@ class BandBankTrainer:
             zu, direct = data['dataset'].slot_ordered(*order)
         else:
             zu, direct = z[:Ku], data['target_early_response'][:, :Ku]
-        Y = bank.delay_line_responses(zu, QQ)
+        Y = bank.delay_line_responses(zu, QQ, Q)
         filt = self._filter_on(Ku, order)
         if fused and side is not None:
             main.wait_event(mlp_done)

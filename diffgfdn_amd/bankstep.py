@@ -81,6 +81,8 @@ class FusedBankStep:
         """Blocks of <= 4 lines: any grid; blocks of 5..8 lines: grids on the unit circle only (``run`` refuses others, and
         the trainer's configuration is the only place that knows before the first batch arrives)."""
         bank = trainer.net
+        if bank.coupled:
+            return False        # (the records are those of independent blocks: A must be block-diagonal)
         if bank.num_delay_lines_per_group > 4 and getattr(trainer.config, 'reduced_pole_radius', 1.0) != 1.0:
             return False
         return (bank.num_delay_lines_per_group <= 8 and bank.num_groups <= 4

@@ -85,6 +85,26 @@ class OrthoParam(torch.autograd.Function):
         return ops.ortho_bwd(M, gQ.contiguous(), gQQ.contiguous(), Q).to(M.dtype)
 
 
+class CoupledFeedback(torch.autograd.Function):
+    """(A, Phi) of ``nbands`` SCALAR-coupled bands: A = block_M o kron(Phi, 1), Phi = ND_Unitary(clamp(alpha))
+    (feedback_loop.py:39-87, :393-455) from the rotations Q (nbands G, n, n) and the angles alpha (nbands, G (G - 1) / 2),
+    one HIP kernel each way (csrc/coupling.hip).  Phi is reported, not differentiated."""
+
+    @staticmethod
+    def forward(ctx, Q, alpha, G: int, nper: int, nbands: int):
+        A, Phi = ops.coupled_feedback_fwd(Q, alpha, G, nper, nbands)
+        ctx.save_for_backward(Q, alpha)
+        ctx.cfg = (G, nper, nbands)
+        ctx.mark_non_differentiable(Phi)
+        return A, Phi
+
+    @staticmethod
+    def backward(ctx, gA, _gPhi):
+        Q, alpha = ctx.saved_tensors
+        gQ, galpha = ops.coupled_feedback_bwd(Q, alpha, *ctx.cfg, gA.contiguous())
+        return gQ.to(Q.dtype), galpha.to(alpha.dtype).reshape(alpha.shape), None, None, None
+
+
 class RowNormalise(torch.autograd.Function):
     """w / (||w||_2 + 1e-6) over the last axis (reference spatial_sampling/model.py:117-190 ``normalise_weights``): one
     launch each way instead of 3 + 11 tensor operators."""

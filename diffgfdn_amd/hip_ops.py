@@ -86,6 +86,44 @@ def ortho_bwd(M, gQ=None, gQQ=None, Q=None):
     return gM
 
 
+def _coupled_args(Q, alpha, G: int, nper: int, nbands: int, what: str):
+    Q, alpha = _f(Q), _f(alpha)
+    if min(G, nper, nbands) <= 0:
+        raise RuntimeError(f"{what}: G, nper and nbands must be positive")
+    if tuple(Q.shape) != (nbands * G, nper, nper) or alpha.numel() != nbands * (G * (G - 1) // 2):
+        raise RuntimeError(f"{what}: Q must be (nbands G, nper, nper) and alpha (nbands, G (G - 1) / 2)")
+    return Q, alpha.reshape(nbands, G * (G - 1) // 2)
+
+
+def coupled_feedback_fwd(Q, alpha, G: int, nper: int, nbands: int = 1):
+    """SCALAR-coupled feedback matrices of ``nbands`` bands in one launch (csrc/coupling.hip).
+    Q (nbands G, nper, nper) rotations, alpha (nbands, G (G - 1) / 2) Givens angles -> (A (nbands, N, N), Phi (nbands, G, G)):
+    A[(i,a),(j,c)] = Phi_ij (Q_i Q_j)[a,c], Phi = ND_Unitary(clamp(alpha, -pi, pi)) (feedback_loop.py:39-87, :393-455)."""
+    _need_gpu(Q, alpha)
+    Q, alpha = _coupled_args(Q, alpha, G, nper, nbands, "coupled_feedback_fwd")
+    N = G * nper
+    A = torch.empty((nbands, N, N), dtype=_f32, device=Q.device)
+    Phi = torch.empty((nbands, G, G), dtype=_f32, device=Q.device)
+    _lib.check(_lib.load().gfdn_coupled_feedback_fwd(_p(Q), _p(alpha) if alpha.numel() else None, nbands, G, nper, _p(A),
+                                                     _p(Phi), _stream()), "gfdn_coupled_feedback_fwd")
+    return A, Phi
+
+
+def coupled_feedback_bwd(Q, alpha, G: int, nper: int, nbands: int, gA):
+    """-> (gQ (nbands G, nper, nper), galpha (nbands, G (G - 1) / 2)) of ``coupled_feedback_fwd`` for gA (nbands, N, N)."""
+    _need_gpu(Q, alpha, gA)
+    Q, alpha = _coupled_args(Q, alpha, G, nper, nbands, "coupled_feedback_bwd")
+    gA = _f(gA)
+    if gA.numel() != nbands * (G * nper) ** 2:
+        raise RuntimeError("coupled_feedback_bwd: gA must be (nbands, N, N)")
+    gQ = torch.empty_like(Q)
+    galpha = torch.empty_like(alpha)
+    none_if_empty = lambda t: _p(t) if t.numel() else None
+    _lib.check(_lib.load().gfdn_coupled_feedback_bwd(_p(Q), none_if_empty(alpha), nbands, G, nper, _p(gA), _p(gQ),
+                                                     none_if_empty(galpha), _stream()), "gfdn_coupled_feedback_bwd")
+    return gQ, galpha
+
+
 def solve_fwd(turns, logr, A, delays, inv_gamma, b, transpose=False, inv_gamma_bins=None,
               precise: bool = False) -> torch.Tensor:
     """A (nblk,nper,nper) f32, delays/inv_gamma/b (N,) f32 -> Y (K,N) complex64.

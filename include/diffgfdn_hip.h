@@ -57,6 +57,23 @@ int gfdn_ortho_bwd(const float* M, int G, int n, const float* gQ, const float* g
 int gfdn_ortho_bwd_add(const float* M, int G, int n, const float* gQ, const float* gQQ, const float* Q,
                        const float* gM_add, float* gM, void* stream);
 
+/* ---- coupled feedback matrices of a band bank  (feedback_loop.py:39-87, :393-455; run_subband_training_treble.py:143-146) --
+ * SCALAR inter-group coupling of every band in one launch (one workgroup per band, float64 in LDS, no atomics: the same
+ * inputs give the same bits, and a band's result does not depend on the other bands of the launch).
+ * Q (nbands G, nper, nper): the rotations expm(skew(M_g)) of gfdn_ortho_fwd, band-major; alpha (nbands, G (G - 1) / 2): the
+ * Givens angles, clamped to [-pi, pi] here.  Phi (nbands, G, G) = U_G with U_1 = 1, U_m = (R_{m-2} .. R_0) diag(U_{m-1}, 1),
+ * R_i the rotation of the (i, m-1) plane by alpha[(m-1)(m-2)/2 + i]: [i,i] = c, [i,m-1] = -s, [m-1,i] = s, [m-1,m-1] = c.
+ * A (nbands, N, N), N = G nper:  A[(i,a),(j,c)] = Phi_ij sum_b Q_i[a,b] Q_j[b,c]; G = 1: the block unscaled (the reference
+ * returns block_M), Phi = 1, alpha / galpha may be NULL.
+ * Backward: gA (nbands, N, N) -> gQ (nbands G, nper, nper), gQ_g = sum_j Phi_gj gA_gj Q_j^T + sum_i Phi_ig Q_i^T gA_ig, and
+ * galpha (nbands, G (G - 1) / 2) from gPhi_ij = <gA_ij, Q_i Q_j> by a reverse sweep through the Givens chain; the clamp
+ * passes the gradient on the closed interval [-pi, pi] and nowhere else (torch.clamp).
+ * G <= GFDN_MAX_GROUPS and G nper <= GFDN_MAX_BLOCK: GFDN_E_UNSUPPORTED otherwise. */
+int gfdn_coupled_feedback_fwd(const float* Q, const float* alpha, int nbands, int G, int nper, float* A, float* Phi,
+                              void* stream);
+int gfdn_coupled_feedback_bwd(const float* Q, const float* alpha, int nbands, int G, int nper, const float* gA, float* gQ,
+                              float* galpha, void* stream);
+
 /* ---- per-bin resolvent solve  (feedback_loop.py:326-391, model.py:237-240, :615-619) ---
  * For every bin k and diagonal block q (nblk blocks of size nper, N = nblk*nper):
  *     T_k = diag(z_k^{m_i} * inv_gamma_i) - A_q            (transpose = 0)

@@ -45,6 +45,7 @@ from .config import CouplingMatrixType, TrainerConfig
 from .functional import (ColorlessTerms, CoupledFeedback, FrequencyGrid, MlpGains, OrthoParam, OutputStage,
                          ResolventSolve, SubFdnColorless)
 from .bankstep import FusedBankStep
+from .graphstep import GraphedTrainStep
 from .losses import decay_losses, edc_loss, shard_loss_scales
 from .optim import FlatAdam
 
@@ -785,7 +786,6 @@ class BandBankTrainer:
     def graphed(self, dataset: BandStackedDataset, batch_per_band: int, mask_source: str = "device",
                 mask_seed: Optional[int] = None):
         """normalize + train_step of bands x batch_per_band receivers as one HIP-graph replay."""
-        from .trainer import GraphedTrainStep
         return GraphedTrainStep(self, dataset, batch_per_band * self.num_bands, mask_source, mask_seed)
 
     def save_model(self, e: int):

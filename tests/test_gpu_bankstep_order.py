@@ -10,7 +10,14 @@ launch.  A recorder, active while one step is issued, logs in host order
   ["graph_nodes", n]                   the node count of each captured graph (catches ATen launches the wrapper does not see),
 with streams tagged main / side / side2.  tests/golden/bankstep_launch_order.json holds the recorded result of every case; a
 change of the launch chain regenerates it deliberately (BANKSTEP_ORDER_RECORD=<file> writes the logs there) and shows the
-diff."""
+diff.
+
+Cases o, p and q pin the captures that the explicit step does not reach (diffgfdn_amd/graphstep.py): a classic trainer's and a
+coupled bank's step under autograd (GraphedTrainStep) and a DirectionalBank on two lanes.  Their streams belong to several
+objects, so the capture's own stream is "main" and every other one is s1, s2, ... by first appearance, as events are
+numbered.  They were recorded on 92b97af, before these classes moved out of trainer.py, by
+  BANKSTEP_ORDER_RECORD=<file> pytest tests/test_gpu_bankstep_order.py -k "o_ or p_ or q_"
+and merged into the fixture."""
 import contextlib
 import json
 import os
@@ -40,6 +47,10 @@ CASES = {
     # (the normalisation scale inside the receiver gains needs the wave-per-receiver gain network: 8 receivers per band)
     "m_gain_fold": ("full", 8, "capture", ()),
     "n_gain_fold_eight_lines": ("full8", 8, "capture", ()),
+    # captures outside the explicit step: (what is captured, -, "graph", -)
+    "o_classic_trainer": ("classic", None, "graph", ()),                 # N = 16, K = 4 097, 4 receivers, STFT window 512
+    "p_coupled_bank": ("coupled", None, "graph", ()),                    # 3 bands, G = 3, 4 receivers per band
+    "q_directional_bank_two_lanes": ("directional", None, "graph", ()),  # 3 bands on 2 lanes, device-side EDC masks
 }
 
 
@@ -52,18 +63,25 @@ def _launching_entry_points():
 @contextlib.contextmanager
 def _recording(tr, capturing_only=True):
     """Yields the log; ``capturing_only``: entries are taken between capture_begin and capture_end only (the warm-up steps
-    in front of a capture are not part of the replayed order)."""
+    in front of a capture are not part of the replayed order).  ``tr`` None: streams are tagged by first appearance."""
     from diffgfdn_amd import _lib
     from diffgfdn_amd.trainer import _graph_node_count
-    log, events, state = [], [], {"capturing": 0, "nested": 0}
+    log, events, others, state = [], [], [], {"capturing": 0, "nested": 0, "origin": None}
     launching, real = _launching_entry_points(), _lib.load()
 
     def tag(stream):
-        return next((w[1:] for w in ("_side", "_side2") if stream == tr._stream(w)), "main")
+        if tr is not None:
+            return next((w[1:] for w in ("_side", "_side2") if stream == tr._stream(w)), "main")
+        if stream == state["origin"]:
+            return "main"
+        if stream not in others:
+            others.append(stream)
+        return f"s{others.index(stream) + 1}"
 
     def add(*entry):
         if not state["nested"] and (state["capturing"] or not capturing_only):
-            log.append([number(e) if isinstance(e, torch.cuda.Event) else e for e in entry])
+            log.append([number(e) if isinstance(e, torch.cuda.Event) else tag(e) if isinstance(e, torch.cuda.Stream) else e
+                        for e in entry])
 
     def number(ev):
         if not any(e is ev for e in events):
@@ -75,11 +93,12 @@ def _recording(tr, capturing_only=True):
             fn = getattr(real, name)
             if name not in launching:
                 return fn
-            return lambda *a: (add("launch", name, tag(torch.cuda.current_stream())), fn(*a))[1]
+            return lambda *a: (add("launch", name, torch.cuda.current_stream()), fn(*a))[1]
 
     class Graph(torch.cuda.CUDAGraph):
         def capture_begin(self, *a, **kw):
             super().capture_begin(*a, **kw)
+            state["origin"] = state["origin"] or torch.cuda.current_stream()
             state["capturing"] += 1
 
         def capture_end(self):
@@ -92,15 +111,15 @@ def _recording(tr, capturing_only=True):
     orig = (torch.cuda.Event.record, torch.cuda.Stream.wait_event, torch.cuda.Stream.wait_stream, torch.cuda.CUDAGraph)
 
     def record(ev, stream=None):
-        add("record", tag(torch.cuda.current_stream() if stream is None else stream), ev)
+        add("record", torch.cuda.current_stream() if stream is None else stream, ev)
         orig[0](ev, stream)
 
     def wait_event(stream, ev):
-        add("wait_event", tag(stream), ev)
+        add("wait_event", stream, ev)
         orig[1](stream, ev)
 
     def wait_stream(stream, other):
-        add("wait_stream", tag(stream), tag(other))
+        add("wait_stream", stream, other)
         state["nested"] += 1                  # (its own record + wait_event are not entries)
         try:
             orig[2](stream, other)
@@ -131,8 +150,35 @@ def _bank(kind):
                                                                 8: [[0, 3, 1, 5, 2, 4, 0, 3], [1, 4, 2, 0, 5, 3, 1, 4]]}
 
 
+def _record_graph_case(kind):
+    """One capture of a tiny model through the classes of diffgfdn_amd/graphstep.py, set up as the parity tests do"""
+    import warnings
+    from diffgfdn_amd.trainer import DirectionalBank, VarReceiverPosTrainer
+    from tests import test_gpu_bank_coupled as gc
+    from tests import test_gpu_parity as gp
+    if kind == "classic":
+        fx, ds, tc = gp._graphed_step_setup()
+        tr = VarReceiverPosTrainer(gp._grid_model(fx), tc, stft_win=512, capturable=True)
+        capture = tr.graphed(ds, 4, mask_seed=4242).capture, ([0, 1, 2, 3],)
+    elif kind == "coupled":
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", message="BandBankTrainer: this layout", category=RuntimeWarning)
+            _, _, _, _, tr, sds, _ = gc._bank_setup(3)
+        assert tr._fused is None
+        capture = tr.graphed(sds, gc.NPER, mask_seed=777).capture, (sds.global_rows(gc.SELS),)
+    else:
+        capture = DirectionalBank(*gp._directional_bands(mask=True), lanes=2, mask_seed=977).capture, ()
+    with _recording(None) as log:
+        capture[0](*capture[1])
+    torch.cuda.synchronize()
+    assert sum(e[0] == "launch" for e in log) >= 8 and sum(e[0] == "graph_nodes" for e in log) == 1, log
+    return log
+
+
 def _record_case(case):
     kind, per, what, off = CASES[case]
+    if what == "graph":
+        return _record_graph_case(kind)
     tr, sds, sels = _bank(kind)
     assert tr._fused is not None
     for name in off:

@@ -190,12 +190,11 @@ def test_f14_learnable_decay_times():
     assert net.feedback_loop.common_decay_times.grad is not None
 
 
-def test_graphed_step_equals_eager_step():
-    """HIP-graph replay of normalize + train_step == the eager step (same masks, same state)."""
+def _graphed_step_setup():
+    """(fixture, dataset, trainer configuration) of the graphed classic step: N = 16, K = 4 097, 12 receivers, EDC mask"""
     from diffgfdn_amd.config import TrainerConfig
     from diffgfdn_amd.dataloader import MultiRIRDataset, RoomDataset
     from diffgfdn_amd.synthetic import synthetic_room
-    from diffgfdn_amd.trainer import VarReceiverPosTrainer
     fx = load("f234_n16_k4097_cp.npz")
     room = synthetic_room(12, 4, 8000.0, 5000, seed=2)
     ds = MultiRIRDataset(DEV, RoomDataset(4, 8000.0, room["source_position"], room["receiver_position"],
@@ -204,6 +203,13 @@ def test_graphed_step_equals_eager_step():
                        use_colorless_loss=True, use_asym_spectral_loss=True, edc_loss_weight=10.0,
                        sparsity_loss_weight=2.0, use_edc_mask=True, train_dir="/tmp/gfdn_t", ir_dir="/tmp/gfdn_a",
                        device="cuda")
+    return fx, ds, tc
+
+
+def test_graphed_step_equals_eager_step():
+    """HIP-graph replay of normalize + train_step == the eager step (same masks, same state)."""
+    from diffgfdn_amd.trainer import VarReceiverPosTrainer
+    fx, ds, tc = _graphed_step_setup()
     results = []
     for mode in ("eager", "graph"):
         net = _grid_model(fx)
@@ -233,19 +239,9 @@ def test_graphed_step_equals_eager_step():
 def test_graphed_step_device_mask():
     """The graph draws the EDC time mask itself (gfdn_draw_mask): every replay must equal an eager
     step that is handed the mask the Philox restatement predicts for (seed, replay number)."""
-    from diffgfdn_amd.config import TrainerConfig
-    from diffgfdn_amd.dataloader import MultiRIRDataset, RoomDataset
-    from diffgfdn_amd.synthetic import synthetic_room
     from diffgfdn_amd.trainer import VarReceiverPosTrainer
     from tests.helpers import philox_mask
-    fx = load("f234_n16_k4097_cp.npz")
-    room = synthetic_room(12, 4, 8000.0, 5000, seed=2)
-    ds = MultiRIRDataset(DEV, RoomDataset(4, 8000.0, room["source_position"], room["receiver_position"],
-                                          room["rirs"], room["common_decay_times"], nfft=8192, device=DEV))
-    tc = TrainerConfig(batch_size=4, num_freq_bins=8192, lr=1e-3, io_lr=1e-2, coupling_angle_lr=1e-2,
-                       use_colorless_loss=True, use_asym_spectral_loss=True, edc_loss_weight=10.0,
-                       sparsity_loss_weight=2.0, use_edc_mask=True, train_dir="/tmp/gfdn_t", ir_dir="/tmp/gfdn_a",
-                       device="cuda")
+    fx, ds, tc = _graphed_step_setup()
     sels = ([0, 1, 2, 3], [4, 5, 6, 7], [8, 9, 10, 11])
     net = _grid_model(fx)
     tr = VarReceiverPosTrainer(net, tc, stft_win=512, capturable=True)
@@ -446,49 +442,51 @@ def test_directional_graphed_step_equals_eager_step(mask):
         assert int(step.mask_state.item()) == 3          # (one draw per replay; the warm-up draws were undone)
 
 
-@pytest.mark.parametrize("mask", [False, True])
-def test_directional_bank_equals_band_steps(mask):
-    """trainer.DirectionalBank: three bands' directional trainers (different parameters, targets and decay times) stepped by
-    ONE graph with the bands on two lanes == every band's own host-launched train_step, bit for bit (values and state) --
-    the bands are independent models, the graph only changes who launches what beside what."""
+def _directional_bands(mask, nb=3):
+    """(trainers, batches) of ``nb`` directional bands with different parameters, targets and decay times"""
     from diffgfdn_amd.config import CouplingMatrixType, FeedbackLoopConfig, OutputFilterConfig, TrainerConfig
     from diffgfdn_amd.model import DiffDirectionalFDNVarReceiverPos
-    from diffgfdn_amd.trainer import DirectionalBank, DirectionalFDNVarReceiverPosTrainer
+    from diffgfdn_amd.trainer import DirectionalFDNVarReceiverPosTrainer
     fx = load("f6_directional.npz")
     fs = float(fx["fs"])
     batch0 = _to_dev(batch_from(fx))
+    trs, batches = [], []
+    for q in range(nb):
+        torch.manual_seed(900 + q)
+        fl = FeedbackLoopConfig(coupling_matrix_type=CouplingMatrixType.SCALAR, use_zero_coupling=True)
+        of = OutputFilterConfig(use_svfs=False, num_hidden_layers=1, num_neurons_per_layer=8, num_fourier_features=3)
+        net = DiffDirectionalFDNVarReceiverPos(fs, int(fx["G"]), fx["delays"].tolist(), DEV, fl, of,
+                                               ambi_order=int(fx["order"]),
+                                               common_decay_times=(fx["T60"] * (1.0 + 0.15 * q))[None, :],
+                                               use_colorless_loss=True, analysis_matrix=fx["analysis_matrix"])
+        sd = _state(fx)
+        if q:                                          # (band q > 0: the fixture's parameters, perturbed)
+            g = torch.Generator().manual_seed(77 + q)
+            sd = {k: (v + 0.05 * torch.randn(v.shape, generator=g).to(v.dtype) if v.is_floating_point() and
+                      k in ("input_gains", "output_gains", "feedback_loop.M") else v) for k, v in sd.items()}
+        net.load_state_dict(sd, strict=True)
+        net = net.to(DEV)
+        tc = TrainerConfig(use_colorless_loss=True, edc_loss_weight=1.0 + q, use_edc_mask=mask, lr=1e-3, io_lr=1e-2,
+                           train_dir=f"/tmp/gfdn_t/db{q}", ir_dir=f"/tmp/gfdn_a/db{q}", device="cuda")
+        tr = DirectionalFDNVarReceiverPosTrainer(net, tc, capturable=True)
+        crit = tr.criterion[0]
+        crit.edc_len_samps = int(float(fx["edc_len_ms"]) * 1e-3 * fs)
+        b = dict(batch0)
+        b["target_common_slope_amps"] = torch.tensor(fx["amps"]).to(DEV) * (1.0 + 0.2 * q)
+        trs.append(tr), batches.append(b)
+    return trs, batches
+
+
+@pytest.mark.parametrize("mask", [False, True])
+def test_directional_bank_equals_band_steps(mask):
+    """graphstep.DirectionalBank: three bands' directional trainers (different parameters, targets and decay times) stepped by
+    ONE graph with the bands on two lanes == every band's own host-launched train_step, bit for bit (values and state) --
+    the bands are independent models, the graph only changes who launches what beside what."""
+    from diffgfdn_amd.trainer import DirectionalBank
     nb = 3
-
-    def build():
-        trs, batches = [], []
-        for q in range(nb):
-            torch.manual_seed(900 + q)
-            fl = FeedbackLoopConfig(coupling_matrix_type=CouplingMatrixType.SCALAR, use_zero_coupling=True)
-            of = OutputFilterConfig(use_svfs=False, num_hidden_layers=1, num_neurons_per_layer=8, num_fourier_features=3)
-            net = DiffDirectionalFDNVarReceiverPos(fs, int(fx["G"]), fx["delays"].tolist(), DEV, fl, of,
-                                                   ambi_order=int(fx["order"]),
-                                                   common_decay_times=(fx["T60"] * (1.0 + 0.15 * q))[None, :],
-                                                   use_colorless_loss=True, analysis_matrix=fx["analysis_matrix"])
-            sd = _state(fx)
-            if q:                                          # (band q > 0: the fixture's parameters, perturbed)
-                g = torch.Generator().manual_seed(77 + q)
-                sd = {k: (v + 0.05 * torch.randn(v.shape, generator=g).to(v.dtype) if v.is_floating_point() and
-                          k in ("input_gains", "output_gains", "feedback_loop.M") else v) for k, v in sd.items()}
-            net.load_state_dict(sd, strict=True)
-            net = net.to(DEV)
-            tc = TrainerConfig(use_colorless_loss=True, edc_loss_weight=1.0 + q, use_edc_mask=mask, lr=1e-3, io_lr=1e-2,
-                               train_dir=f"/tmp/gfdn_t/db{q}", ir_dir=f"/tmp/gfdn_a/db{q}", device="cuda")
-            tr = DirectionalFDNVarReceiverPosTrainer(net, tc, capturable=True)
-            crit = tr.criterion[0]
-            crit.edc_len_samps = int(float(fx["edc_len_ms"]) * 1e-3 * fs)
-            b = dict(batch0)
-            b["target_common_slope_amps"] = torch.tensor(fx["amps"]).to(DEV) * (1.0 + 0.2 * q)
-            trs.append(tr), batches.append(b)
-        return trs, batches
-
     res = {}
     for mode in ("eager", "bank"):
-        trs, batches = build()
+        trs, batches = _directional_bands(mask, nb)
         bank = DirectionalBank(trs, batches, lanes=2, mask_seed=977).capture() if mode == "bank" else None
         if mask and mode == "eager":          # (the bank's device generators, band q seeded 977 + q, launched from the host)
             for q, tr in enumerate(trs):

@@ -224,6 +224,7 @@ SIGNATURES = {
     "gfdn_edc_loss_pairs_banded": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_float,
                                            c_float, _P, _P, _P, _P]),
     "gfdn_draw_mask_banded": (c_int, [ctypes.c_ulonglong, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
+    "gfdn_render_mix": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
 }
 
 _lib = None

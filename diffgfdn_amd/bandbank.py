@@ -213,6 +213,48 @@ class BandBank(nn.Module):
         return MlpGains.apply(positions, rows, self._freq_pi, H, n_hidden, self.num_groups, lo, hi,
                               self.output_scalars_w)
 
+    # -- full-band render (subband.infer_bank): the model's side of y[r] = D[r] + sum_s W[r][s] C[s] -------------------
+    @torch.no_grad()
+    def filtered_group_signals(self, z: torch.Tensor, taps: torch.Tensor) -> torch.Tensor:
+        """C (bands*G, nfft + M - 1): every band's group transfer functions T_{q,g} = sum_{line in g} c_line y_line (the
+        bank's solve of ALL bands, zero-coupling or coupled, and the output stage with identity receiver gains, as
+        ``sub_fdn_group_sums``) brought to the time domain (h = irfft(T), n = nfft = 2 (K - 1): utils.py:149-179) and
+        through the band's reconstructing FIR ``taps[q]`` (fftconvolve(h, taps, 'full'),
+        run_subband_training_treble.py:321-324) -- bands x G signals, whatever the number of receivers.  The rows' pitch
+        is a multiple of four samples (csrc/render.hip reads them 16 bytes per lane)."""
+        from .subband import full_convolve
+        nb, G = self.num_bands, self.num_groups
+        K = z.shape[-1]
+        nfft = 2 * (K - 1)
+        if nfft < 16 or nfft & (nfft - 1):
+            raise ValueError("filtered_group_signals: the frequency grid of a power-of-two transform (K = nfft / 2 + 1)")
+        if taps.dim() != 2 or taps.shape[0] != nb:
+            raise ValueError("filtered_group_signals: taps (bands, M)")
+        Q, QQ = self.rotations()
+        Y = self.delay_line_responses(z, QQ, Q)
+        T = OutputStage.apply(Y, self.output_gains.view(-1), self._eye, self.num_delay_lines_per_group, None, None, None, nb)
+        h = ops.irfft_pow2_fwd(T, nfft)                                    # (bands*G, nfft)
+        L = nfft + taps.shape[1] - 1
+        C = torch.empty((nb * G, (L + 3) // 4 * 4), dtype=torch.float32, device=h.device)[:, :L]
+        for q in range(nb):
+            C[q * G:(q + 1) * G] = full_convolve(h[q * G:(q + 1) * G], taps[q])
+        return C
+
+    @torch.no_grad()
+    def render_gains(self, positions: torch.Tensor, R: int, rows: Optional[torch.Tensor] = None, chunk: int = 4096):
+        """W (len(rows) or R, bands*G): column band G + g = band's gain network at the receiver, group g -- ``group_gains``
+        for all receivers of all bands (``positions`` (bands*R, 3) band-major, ``rows``: receivers < R), ``chunk`` receivers
+        per band and launch (bounded temporaries)."""
+        nb, G = self.num_bands, self.num_groups
+        sel = torch.arange(R, device=positions.device) if rows is None else rows
+        out = torch.empty((sel.numel(), nb * G), dtype=torch.float32, device=positions.device)
+        base = torch.arange(nb, device=positions.device).view(nb, 1) * R
+        for i0 in range(0, sel.numel(), chunk):
+            part = sel[i0:i0 + chunk]
+            g = self.group_gains(positions, (base + part.view(1, -1)).reshape(-1).contiguous())      # (bands*B, G)
+            out[i0:i0 + part.numel()] = g.view(nb, part.numel(), G).permute(1, 0, 2).reshape(part.numel(), nb * G)
+        return out
+
 
 class BandStackedDataset:
     """The bands' MultiRIRDataset stores stacked band-major: row = band * R + receiver.
@@ -337,6 +379,38 @@ class BandStackedDataset:
             self._direct_time = (key, out, filt)          # (the entry keeps the filter alive: the key is its ADDRESS, and a
                                                           # freed filter's block handed to another one would be a false hit)
         return self._direct_time[1]
+
+    def direct_render(self, taps: torch.Tensor, chunk: int = 32) -> torch.Tensor:
+        """D (R, nfft + M - 1) float32: every receiver's direct path rendered through ALL bands,
+        D[r] = sum_q fftconvolve(irfft(early[q R + r], n = 2 (K - 1)), taps[q], 'full') -- the part of the full-band room
+        impulse responses (run_subband_training_treble.py:207-375: get_response, :321-324, :358) that no parameter
+        touches; ``taps`` (bands, M) the bands' reconstructing FIRs.  A constant of the dataset and the taps like
+        ``direct_time``: built once, ``chunk`` receivers at a time, and cached per taps -- by the tensor's address, shape
+        and version (the entry keeps the tensor alive, as ``direct_time`` keeps its filter), else by value against a copy
+        of the taps the entry was built from: other taps, or the same tensor edited in place, rebuild it.  The rows'
+        pitch is a multiple of four samples (csrc/render.hip reads them 16 bytes per lane)."""
+        from .subband import full_convolve
+        if taps.dim() != 2 or taps.shape[0] != self.num_bands or taps.dtype != torch.float32:
+            raise ValueError("direct_render: taps (bands, M) float32")
+        key = (taps.data_ptr(), tuple(taps.shape), taps._version)
+        cache = getattr(self, '_direct_render', None)
+        if cache is not None and (cache[0] == key or (cache[0][1] == key[1] and torch.equal(cache[3], taps))):
+            return cache[1]
+        E = self.early_rir_mag_response
+        R, K = self.R, E.shape[1]
+        nfft = 2 * (K - 1)
+        if E.shape[0] != self.num_bands * R or nfft < 16 or nfft & (nfft - 1):
+            raise RuntimeError("direct_render: the early-response store does not match bands x receivers of a power-of-two "
+                               "transform")
+        L = nfft + taps.shape[1] - 1
+        out = torch.zeros((R, (L + 3) // 4 * 4), dtype=torch.float32, device=E.device)[:, :L]
+        for r0 in range(0, R, chunk):
+            r1 = min(r0 + chunk, R)
+            for q in range(self.num_bands):
+                h = ops.irfft_pow2_fwd(E[q * R + r0:q * R + r1], nfft)
+                out[r0:r1] += full_convolve(h, taps[q])
+        self._direct_render = (key, out, taps, taps.detach().clone())
+        return out
 
     def edr_target_tiled(self) -> torch.Tensor:
         """The target EDR store in the tiled cell order of csrc/edrlin.hip (``ops.spec_tile``); built once, cached."""

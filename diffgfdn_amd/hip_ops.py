@@ -1935,6 +1935,51 @@ def rfft_pow2(x, n: int) -> torch.Tensor:
     return X
 
 
+def _render_rows(t, name: str, n: int) -> torch.Tensor:
+    """a (rows, >= n) float32 matrix whose rows are contiguous; a row-strided view is consumed in place"""
+    if t.dtype != _f32 or t.dim() != 2 or t.shape[1] < n or t.stride(1) != 1 or t.stride(0) < n or t.stride(0) >= 2 ** 31:
+        raise RuntimeError(f"render_mix: {name} must be a float32 matrix with contiguous rows of at least {n} samples")
+    return t.detach()
+
+
+def render_mix(d, w, c, rows=None, out=None) -> torch.Tensor:
+    """out (R, n) = d[rows] + w @ c: the full-band render of a band bank (csrc/render.hip).  d (.., >= n) the direct paths
+    of the dataset's receivers, c (S, n) the filtered group signals, w (R, S) the receiver gains; ``rows`` (R,) int64 picks
+    and orders the rows of d (default: row i for receiver i).  d, c, out may be row-strided views.  More than 32 signals go
+    in chunks of 32, every chunk adding to what the one before left in ``out``; ``out`` may be ``d`` itself when there are
+    no ``rows``."""
+    _need_gpu(d, w, c, rows, out)
+    w = _f(w)
+    if w.dim() != 2 or c.dim() != 2 or c.shape[0] != w.shape[1] or w.numel() == 0 or c.shape[1] == 0:
+        raise RuntimeError("render_mix: w (R, S) and c (S, n) expected")
+    R, S = w.shape
+    n = c.shape[1]
+    d, c = _render_rows(d, "d", n), _render_rows(c, "c", n)
+    rows = _rows(rows, R, d.shape[0])
+    if rows is None and d.shape[0] < R:
+        raise RuntimeError("render_mix: d must have one row per receiver (or pass rows)")
+    if rows is not None and (int(rows.min()) < 0 or int(rows.max()) >= d.shape[0]):
+        raise RuntimeError("render_mix: rows outside the direct-path store")
+    if out is None:
+        out = torch.empty((R, n), dtype=_f32, device=d.device)
+    else:
+        out = _render_rows(out, "out", n)
+        if out.shape[0] != R or out.shape[1] != n:
+            raise RuntimeError("render_mix: out must be (R, n)")
+        if out.untyped_storage().data_ptr() == d.untyped_storage().data_ptr():
+            # one storage: only as THE SAME rows (every thread then writes what it read)
+            if rows is not None or out.data_ptr() != d.data_ptr() or out.stride(0) != d.stride(0):
+                raise RuntimeError("render_mix: out may alias d only as the same rows, without a row index")
+    lib = _lib.load()
+    src, src_rows = d, rows
+    for s0 in range(0, S, 32):
+        wc = w if S <= 32 else w[:, s0:s0 + 32].contiguous()
+        _lib.check(lib.gfdn_render_mix(_p(src), src.stride(0), _p(src_rows), _p(wc), c[s0:].data_ptr(), c.stride(0), R,
+                                       wc.shape[1], n, _p(out), out.stride(0), _stream()), "gfdn_render_mix")
+        src, src_rows = out, None
+    return out
+
+
 def rfft_pow2_f64(x, n: int, kout: Optional[int] = None) -> torch.Tensor:
     """x (batch, T <= n) float64 -> the first ``kout`` (default n / 2 + 1) bins of rfft(x, n) as complex128 (csrc/fft64.hip:
     float64 radix-2 passes -- dataset constants only, speed is not the point)."""

@@ -74,6 +74,40 @@ def infer_bands(freqs: Sequence[float], load_band: Callable[[float], tuple], ran
     return sum_bands(local, group=group, dst=dst, device=device)
 
 
+@torch.no_grad()
+def infer_bank(bank, dataset, taps, rows=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The full-band RIRs of a trained band bank in one pass: what ``infer_bands`` returns for ``bank.nets``, the bands'
+    datasets and ``taps`` (the reference's ``inferencing``, :207-375), without leaving the bank.  Neither irfft nor the
+    convolution depends on the receiver, which enters only through its G gains per band:
+
+        y[r] = sum_q fftconvolve(irfft(H_q[r]), taps_q) = D[r] + sum_{q,g} gain_q[r][g] (irfft(T_{q,g}) (*) taps_q)
+
+    ``D = dataset.direct_render(taps)`` is a constant of the dataset (built on the first call, cached per taps), the model
+    contributes bands x G filtered group signals (``bank.filtered_group_signals``) and all receivers are one product
+    Y = D + W C (``hip_ops.render_mix``, csrc/render.hip) with the gains W of ``bank.render_gains``.
+
+    ``bank``: BandBank; ``dataset``: the BandStackedDataset of its bands; ``taps``: (bands, M) tensor or a sequence of
+    equal-length tensors; ``rows``: receivers to render, in this order (default: all R) -- a job that spreads the receivers
+    over its ranks passes every rank its share, no collective is involved; ``out``: (len(rows) or R, nfft + M - 1) float32
+    buffer to fill.  Returns (len(rows) or R, nfft + M - 1) float32 on the bank's device."""
+    dev = bank.input_gains.device
+    if not torch.is_tensor(taps):
+        taps = torch.stack([torch.as_tensor(t) for t in taps])
+    taps = taps.detach().to(device=dev, dtype=torch.float32)
+    if taps.dim() != 2 or taps.shape[0] != bank.num_bands or dataset.num_bands != bank.num_bands:
+        raise ValueError("infer_bank: one row of taps and one dataset per band of the bank")
+    taps = taps.contiguous()
+    sel = None
+    if rows is not None:
+        sel = torch.as_tensor(rows, dtype=torch.long, device=dev).reshape(-1).contiguous()
+        if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= dataset.R:
+            raise ValueError("infer_bank: rows must name receivers of the dataset")
+    D = dataset.direct_render(taps)
+    C = bank.filtered_group_signals(dataset.z_values, taps)
+    W = bank.render_gains(dataset.norm_listener_position, dataset.R, sel)
+    return ops.render_mix(D, W, C, rows=sel, out=out)
+
+
 def sum_bands(local_band_rirs: Sequence[torch.Tensor], group=None, dst: int = 0, device=None) -> Optional[torch.Tensor]:
     """Sum of the filtered RIRs over ALL bands (reference :358 ``groupby('position').apply(sum)``):
     local sum over this rank's bands, then one reduce to ``dst``.  Returns the total on ``dst``,

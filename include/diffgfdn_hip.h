@@ -1024,6 +1024,18 @@ int gfdn_adam_step_mirrored(float* p, const float* g, float* m, float* v, const 
                             const float* lr_seg, float* step_count, float* mirror, int n, float beta1, float beta2,
                             float eps, unsigned int* block_counter, void* stream);
 
+/* ---- full-band render of a band bank  (run_subband_training_treble.py:207-375 ``inferencing``: get_response, fftconvolve with
+ * the band's reconstructing FIR :321-324, sum over the bands per receiver :358) as one skinny product (csrc/render.hip):
+ *     out[i][t] = d[rows ? rows[i] : i][t] + sum_{s < S} w[i S + s] c[s ld_c + t],   i < R, t < n, float32,
+ * d (.., ld_d) the receivers' direct paths through all bands (a constant of the dataset), c (S, ld_c) the bank's filtered
+ * group signals, w (R, S) the receiver gains.  acc = d, then acc = fma(w_s, c_s, acc) for s = 0 .. S-1: the same bits for a
+ * receiver whatever the other receivers of the launch.  S <= 32 per launch (GFDN_E_UNSUPPORTED above): a caller with more
+ * signals launches in chunks and passes out as the next chunk's d with rows = NULL -- out may BE d then (every thread
+ * writes the elements it read); with rows, d and out must not be the same buffer (GFDN_E_BADARG).  16-byte accesses when d, c,
+ * out are 16-byte aligned and the pitches multiples of 4, 4-byte accesses otherwise; pitches >= n; rows is not range-checked. */
+int gfdn_render_mix(const float* d, int ld_d, const long long* rows, const float* w, const float* c, int ld_c, int R, int S,
+                    int n, float* out, int ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,7 @@ SIGNATURES = {
                                            c_float, _P, _P, _P, _P]),
     "gfdn_draw_mask_banded": (c_int, [ctypes.c_ulonglong, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
     "gfdn_render_mix": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "gfdn_edc_err": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
 }
 
 _lib = None

@@ -241,6 +241,19 @@ class BandBank(nn.Module):
         return C
 
     @torch.no_grad()
+    def analysis_group_signals(self, z: torch.Tensor, taps: torch.Tensor, analysis_taps: torch.Tensor,
+                               length: int) -> torch.Tensor:
+        """Ck (A, bands*G, length): ``filtered_group_signals(z, taps)`` through every analysis band
+        (``subband.band_split``: the first ``length`` samples of the causal convolution with analysis_taps[k]) -- the model's
+        side of a_k * y[r] = a_k * D[r] + sum_s W[r][s] (a_k * C_s), A x bands x G signals whatever the number of receivers
+        (subband.edc_error_bank, csrc/edcerr.hip).  The rows' pitch is a multiple of four samples."""
+        from .subband import band_split
+        C = self.filtered_group_signals(z, taps)
+        Ck = ops.empty_bands(analysis_taps.shape[0], C.shape[0], int(length), C.device)
+        band_split(C, analysis_taps, length, out=Ck.permute(1, 0, 2))
+        return Ck
+
+    @torch.no_grad()
     def render_gains(self, positions: torch.Tensor, R: int, rows: Optional[torch.Tensor] = None, chunk: int = 4096):
         """W (len(rows) or R, bands*G): column band G + g = band's gain network at the receiver, group g -- ``group_gains``
         for all receivers of all bands (``positions`` (bands*R, 3) band-major, ``rows``: receivers < R), ``chunk`` receivers
@@ -410,6 +423,73 @@ class BandStackedDataset:
                 h = ops.irfft_pow2_fwd(E[q * R + r0:q * R + r1], nfft)
                 out[r0:r1] += full_convolve(h, taps[q])
         self._direct_render = (key, out, taps, taps.detach().clone())
+        return out
+
+    # -- EDC matching error over the grid (subband.edc_error_bank): the dataset's two constants ------------------------
+    @staticmethod
+    def _tensor_key(t: torch.Tensor):
+        return (t.data_ptr(), tuple(t.shape), t._version)
+
+    @staticmethod
+    def _same_tensor(entry, t: torch.Tensor) -> bool:
+        """``direct_render``'s cache rule for one input: entry = (key, the tensor itself -- kept alive, its address is the
+        key --, a copy of its values): the same address, shape and version, else equal values"""
+        key = BandStackedDataset._tensor_key(t)
+        return entry[0] == key or (entry[0][1] == key[1] and entry[2].dtype == t.dtype and entry[2].device == t.device
+                                   and torch.equal(entry[2], t))
+
+    @staticmethod
+    def _tensor_entry(t: torch.Tensor):
+        return (BandStackedDataset._tensor_key(t), t, t.detach().clone())
+
+    def direct_band_render(self, taps: torch.Tensor, analysis_taps: torch.Tensor, length: int) -> torch.Tensor:
+        """Dk (R, A, length) float32: ``direct_render(taps)`` through every analysis band,
+        Dk[r][k] = (analysis_taps[k] * D[r])[:length] (``subband.band_split``: the first ``length`` samples of the causal
+        convolution) -- the part of the estimate's band signals a_k * y[r] = a_k * D[r] + sum_s W[r][s] (a_k * C_s) that no
+        parameter touches (plot.py:632-661 ``get_edc_error``'s octave filtering of the estimate).  A constant of the dataset
+        and both sets of taps: built once from ``direct_render(taps)`` and cached under ``direct_render``'s rule for BOTH
+        tensors (address, shape and version, else by value); other taps or analysis taps, or either edited in place,
+        rebuild it.  2.25 GB at 838 receivers x 7 bands x 96 000 samples.  The rows' pitch is a multiple of four samples."""
+        from .subband import band_split
+        if analysis_taps.dim() != 2 or analysis_taps.dtype != torch.float32:
+            raise ValueError("direct_band_render: analysis_taps (A, Ma) float32")
+        length = int(length)
+        cache = getattr(self, '_direct_band_render', None)
+        if (cache is not None and cache[0] == length and self._same_tensor(cache[2], taps)
+                and self._same_tensor(cache[3], analysis_taps)):
+            return cache[1]
+        self._direct_band_render = None                                    # (never two of them alive)
+        out = band_split(self.direct_render(taps), analysis_taps, length)
+        self._direct_band_render = (length, out, self._tensor_entry(taps), self._tensor_entry(analysis_taps))
+        return out
+
+    def edc_error_target(self, measured, analysis_taps: torch.Tensor, length: int, chunk: int = 32) -> torch.Tensor:
+        """Tdb (R, A, length) float32: the measured side of the EDC matching error (plot.py:632-661), the EDC in dB of every
+        measured RIR in every analysis band, dB(sum_{u >= t} ((analysis_taps[k] * measured[r])[:length])[u]^2) with
+        dB(v) = max(10 log10(|v| + eps_f32), -200) (utils.py:16-40) -- through the SAME kernel that scores the estimate
+        (csrc/edcerr.hip, mode "curve"), ``chunk`` receivers at a time.  ``measured`` (R, T): a tensor or numpy.  Cached like
+        ``direct_band_render`` per (measured, analysis_taps, length): a float32 tensor on this device is recognised by its
+        address, shape and version without a host sync; anything else is uploaded and compared by value.  2.25 GB at 838
+        receivers x 7 bands x 96 000 samples."""
+        from .subband import band_split
+        if analysis_taps.dim() != 2 or analysis_taps.dtype != torch.float32:
+            raise ValueError("edc_error_target: analysis_taps (A, Ma) float32")
+        m = torch.as_tensor(measured)
+        if m.dim() != 2 or m.shape[0] != self.R:
+            raise ValueError("edc_error_target: measured (R, T), one row per receiver")
+        dev = self.early_rir_mag_response.device
+        if m.device != dev or m.dtype != torch.float32:
+            m = m.detach().to(device=dev, dtype=torch.float32)
+        length = int(length)
+        cache = getattr(self, '_edc_error_target', None)
+        if (cache is not None and cache[0] == length and self._same_tensor(cache[3], analysis_taps)
+                and self._same_tensor(cache[2], m)):
+            return cache[1]
+        self._edc_error_target = None
+        out = ops.empty_bands(self.R, analysis_taps.shape[0], length, dev)
+        for r0 in range(0, self.R, chunk):
+            ops.edc_curve_db(band_split(m[r0:r0 + chunk], analysis_taps, length), length, out=out[r0:r0 + chunk])
+        self._edc_error_target = (length, out, self._tensor_entry(m), self._tensor_entry(analysis_taps))
         return out
 
     def edr_target_tiled(self) -> torch.Tensor:

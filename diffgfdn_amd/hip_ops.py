@@ -1980,6 +1980,93 @@ def render_mix(d, w, c, rows=None, out=None) -> torch.Tensor:
     return out
 
 
+def _band_signals(t, name: str, L: int, what: str) -> torch.Tensor:
+    """a (rows, bands, >= L) float32 tensor with contiguous samples and ONE pitch: stride(0) = bands * stride(1)"""
+    if (t.dtype != _f32 or t.dim() != 3 or t.numel() == 0 or t.shape[2] < L or t.stride(2) != 1 or t.stride(1) < L
+            or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)) or t.stride(1) >= 2 ** 31):
+        raise RuntimeError(f"{what}: {name} must be a float32 (rows, bands, >= {L}) tensor with contiguous samples and "
+                           "one row pitch")
+    return t.detach()
+
+
+def _edc_rows(rows, R: int, store_rows: int, what: str, rows_checked: bool):
+    rows = _rows(rows, R, store_rows)
+    if rows is not None and not rows_checked and (int(rows.min()) < 0 or int(rows.max()) >= store_rows):
+        raise RuntimeError(f"{what}: rows outside the store")
+    return rows
+
+
+def empty_bands(rows: int, bands: int, L: int, device) -> torch.Tensor:
+    """(rows, bands, L) float32 view of rows whose pitch is the next multiple of four samples (csrc/edcerr.hip moves them
+    16 bytes per lane)"""
+    return torch.empty((rows, bands, (L + 3) // 4 * 4), dtype=_f32, device=device)[:, :, :L]
+
+
+def edc_error(Dk, Tdb, L: int, W=None, Ck=None, rows=None, out=None, *, rows_checked: bool = False) -> torch.Tensor:
+    """err (R, A): the EDC matching error in dB of every receiver and analysis band (reference plot.py:632-661
+    ``get_edc_error``; csrc/edcerr.hip), err[i][k] = mean_{t < L} |dB(E[t]) - Tdb[row][k][t]| with
+    x = Dk[row][k] + sum_s W[i][s] Ck[k][s], E[t] = sum_{u >= t} x[u]^2, dB(v) = max(10 log10(|v| + eps_f32), -200),
+    row = rows[i] (default i).  Dk (R_store, A, >= L) the analysis-filtered band signals that no parameter touches, Tdb
+    (R_store, A, >= L) the measured side's dB curves (``edc_curve_db``), W (R, S) and Ck (A, S, >= L) the receiver gains
+    and the analysis-filtered group signals -- or neither: Dk already is the estimate's band signals.  S <= 32.  The
+    composed signals and their EDCs are never stored.  ``rows`` is range-checked here (one host sync) unless
+    ``rows_checked``."""
+    what = "edc_error"
+    _need_gpu(Dk, Tdb, W, Ck, rows, out)
+    L = int(L)
+    if L < 1:
+        raise RuntimeError(f"{what}: L >= 1")
+    Dk, Tdb = _band_signals(Dk, "Dk", L, what), _band_signals(Tdb, "Tdb", L, what)
+    A = Dk.shape[1]
+    if Tdb.shape[0] != Dk.shape[0] or Tdb.shape[1] != A:
+        raise RuntimeError(f"{what}: Dk and Tdb must have the same rows and bands")
+    if (W is None) != (Ck is None):
+        raise RuntimeError(f"{what}: W and Ck come together")
+    S = 0
+    if W is not None:
+        W, Ck = _f(W), _band_signals(Ck, "Ck", L, what)
+        if W.dim() != 2 or W.numel() == 0 or Ck.shape[0] != A or Ck.shape[1] != W.shape[1]:
+            raise RuntimeError(f"{what}: W (R, S) and Ck (A, S, >= L) expected")
+        S = W.shape[1]
+        if S > 32:
+            raise RuntimeError(f"{what}: at most 32 group signals per band (render the band signals and pass them as Dk)")
+    R = W.shape[0] if W is not None else (Dk.shape[0] if rows is None else rows.numel())
+    rows = _edc_rows(rows, R, Dk.shape[0], what, rows_checked)
+    if rows is None and Dk.shape[0] < R:
+        raise RuntimeError(f"{what}: Dk must have one row per receiver (or pass rows)")
+    if out is None:
+        out = torch.empty((R, A), dtype=_f32, device=Dk.device)
+    elif out.dtype != _f32 or tuple(out.shape) != (R, A) or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be a contiguous float32 (R, A) tensor")
+    _lib.check(_lib.load().gfdn_edc_err(_p(Dk), Dk.stride(1), _p(rows), _p(W), _p(Ck), 0 if Ck is None else Ck.stride(1),
+                                        _p(Tdb), Tdb.stride(1), R, A, S, L, 0, _p(out), A, _stream()), "gfdn_edc_err")
+    return out
+
+
+def edc_curve_db(Dk, L: int, rows=None, out=None, *, rows_checked: bool = False) -> torch.Tensor:
+    """out (R, A, L): the EDC in dB of the band signals Dk (R_store, A, >= L) themselves, dB(sum_{u >= t} Dk[row][k][u]^2),
+    through the arithmetic of ``edc_error`` (csrc/edcerr.hip, mode "curve": how the measured side's ``Tdb`` is built).
+    Without ``out`` the result is a view of rows whose pitch is a multiple of four samples."""
+    what = "edc_curve_db"
+    _need_gpu(Dk, rows, out)
+    L = int(L)
+    if L < 1:
+        raise RuntimeError(f"{what}: L >= 1")
+    Dk = _band_signals(Dk, "Dk", L, what)
+    A = Dk.shape[1]
+    R = Dk.shape[0] if rows is None else rows.numel()
+    rows = _edc_rows(rows, R, Dk.shape[0], what, rows_checked)
+    if out is None:
+        out = empty_bands(R, A, L, Dk.device)
+    else:
+        out = _band_signals(out, "out", L, what)
+        if tuple(out.shape) != (R, A, L) or out.untyped_storage().data_ptr() == Dk.untyped_storage().data_ptr():
+            raise RuntimeError(f"{what}: out must be (R, A, L), and not in Dk's storage")
+    _lib.check(_lib.load().gfdn_edc_err(_p(Dk), Dk.stride(1), _p(rows), None, None, 0, None, 0, R, A, 0, L, 1, _p(out),
+                                        out.stride(1), _stream()), "gfdn_edc_err")
+    return out
+
+
 def rfft_pow2_f64(x, n: int, kout: Optional[int] = None) -> torch.Tensor:
     """x (batch, T <= n) float64 -> the first ``kout`` (default n / 2 + 1) bins of rfft(x, n) as complex128 (csrc/fft64.hip:
     float64 radix-2 passes -- dataset constants only, speed is not the point)."""

@@ -108,6 +108,156 @@ def infer_bank(bank, dataset, taps, rows=None, out: Optional[torch.Tensor] = Non
     return ops.render_mix(D, W, C, rows=sel, out=out)
 
 
+def band_split(x: torch.Tensor, analysis_taps: torch.Tensor, length: int, chunk: int = 32,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, A, length) float32: the first ``length`` samples of ``full_convolve(x[r], analysis_taps[k])`` for every row
+    and analysis band -- the reference's ``octave_filtering`` (plot.py:632-661) with the filterbank as a declared input:
+    causal FIRs, THE FIRST ``length`` SAMPLES OF THE CAUSAL CONVOLUTION (truncating before or after the filter is the
+    same).  x (rows, T) float32 on the device, analysis_taps (A, Ma).  One forward transform per row, one inverse per row
+    and band, ``chunk`` rows at a time (bounded temporaries).  The rows' pitch is a multiple of four samples
+    (csrc/edcerr.hip moves them 16 bytes per lane); ``out``: any (rows, A, length) float32 view to fill instead."""
+    length = int(length)
+    if x.dim() != 2 or analysis_taps.dim() != 2 or length < 1 or x.shape[1] < 1:
+        raise ValueError("band_split: x (rows, T), analysis_taps (A, Ma), length >= 1")
+    at = analysis_taps.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    A, Ma = at.shape
+    T = min(x.shape[1], length)
+    n = max(16, 1 << (T + Ma - 2).bit_length())
+    m = min(length, n)
+    if out is None:
+        out = ops.empty_bands(x.shape[0], A, length, x.device)
+    elif tuple(out.shape) != (x.shape[0], A, length) or out.dtype != torch.float32:
+        raise ValueError("band_split: out (rows, A, length) float32")
+    if m < length:
+        out[:, :, m:] = 0.0                               # (behind the end of the full convolution)
+    Tf = ops.rfft_pow2(at, n)
+    for r0 in range(0, x.shape[0], chunk):
+        Xf = ops.rfft_pow2(x[r0:r0 + chunk, :T], n)
+        for k in range(A):
+            out[r0:r0 + chunk, k, :m] = ops.irfft_pow2_fwd(Xf * Tf[k], n)[:, :m]
+    return out
+
+
+def _edc_taps(bank, taps, analysis_taps):
+    dev = bank.input_gains.device
+    if not torch.is_tensor(taps):
+        taps = torch.stack([torch.as_tensor(t) for t in taps])
+    if taps.device != dev or taps.dtype != torch.float32 or not taps.is_contiguous():
+        taps = taps.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if analysis_taps is None:
+        return taps, taps
+    if not torch.is_tensor(analysis_taps):
+        analysis_taps = torch.stack([torch.as_tensor(t) for t in analysis_taps])
+    if analysis_taps.device != dev or analysis_taps.dtype != torch.float32 or not analysis_taps.is_contiguous():
+        analysis_taps = analysis_taps.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return taps, analysis_taps
+
+
+def _edc_rows(rows, R: int, dev, what: str):
+    """``rows`` as a checked int64 device vector; host data is checked on the host (no device sync)"""
+    if rows is None:
+        return None
+    sel = torch.as_tensor(rows, dtype=torch.long).reshape(-1)
+    if sel.numel() == 0 or int(sel.min()) < 0 or int(sel.max()) >= R:
+        raise ValueError(f"{what}: rows must name receivers of the dataset")
+    return sel.to(dev).contiguous()
+
+
+def _rmse(err: torch.Tensor) -> torch.Tensor:
+    return torch.linalg.vector_norm(err, dim=0) / float(err.shape[0]) ** 0.5
+
+
+@torch.no_grad()
+def edc_error_bank(bank, dataset, taps, measured, sample_rate: Optional[float] = None, analysis_taps=None, rows=None):
+    """The EDC matching error of a trained band bank over the receiver grid in one pass: the reference's
+    ``plot_edc_error_in_space`` -> ``get_edc_error`` (plot.py:606-757, the metric at :632-661; its "RMSE in matching EDC at
+    ... Hz is ... dB" line) of the bank's full-band render (``infer_bank``) against the measured RIRs.
+
+        L = min(Tx, Ty, int(2 sample_rate))                                                     (plot.py:689-694)
+        x_k[r] = (a_k * measured[r])[:L],  y_k[r] = (a_k * y[r])[:L]        a_k = analysis_taps[k], causal convolution
+        E_k[r][t] = sum_{u >= t} x_k[r][u]^2, likewise for y     (normalize = False, discard_last_zeros = False)
+        dB(v) = max(10 log10(|v| + eps_f32), -200)                              (utils.py:16-40: floor at about -69.2 dB)
+        error_db[r][k] = mean_t |dB(E^x_k[r][t]) - dB(E^y_k[r][t])|,  rmse[k] = ||error_db[:, k]||_2 / sqrt(R)  (:656-661)
+
+    The analysis filterbank is a DECLARED INPUT (the reference's comes from pyfar / slope2noise): ``analysis_taps`` (A, Ma)
+    causal FIRs, default ``taps``; a band signal is the first L samples of the causal convolution.  The filter is linear, so
+    a_k * y[r] = a_k * D[r] + sum_s W[r][s] (a_k * C_s): ``dataset.direct_band_render`` and ``dataset.edc_error_target`` are
+    constants (built on the first call, cached; 2.25 GB EACH at 838 receivers x 7 bands x 96 000 samples), the model
+    contributes A x bands x G signals (``bank.analysis_group_signals``), and csrc/edcerr.hip composes, squares, scans and
+    compares every (receiver, band) without storing the estimate's band signals.  More than 32 group signals: the band
+    signals are rendered with ``hip_ops.render_mix`` into a temporary, 128 receivers at a time.
+
+    ``measured`` (R, Tx): tensor or numpy; pass a float32 device tensor for a steady state without host syncs (anything
+    else is uploaded and compared by value against the cached target's source).  ``sample_rate`` defaults to the bank's;
+    ``rows``: receivers to score, in this order (default all R) -- a job that spreads receivers over ranks passes every rank
+    its share, and the job's rmse is the root of the ranks' summed squares over the total count.  Not covered:
+    ``norm_edc=True``, position re-ordering, the plots, the EDR variant.
+    Returns (error_db (len(rows) or R, A), rmse (A,)) float32 on the bank's device."""
+    dev = bank.input_gains.device
+    taps, at = _edc_taps(bank, taps, analysis_taps)
+    if taps.dim() != 2 or taps.shape[0] != bank.num_bands or dataset.num_bands != bank.num_bands or at.dim() != 2:
+        raise ValueError("edc_error_bank: one row of taps and one dataset per band of the bank; analysis_taps (A, Ma)")
+    fs = float(bank.sample_rate if sample_rate is None else sample_rate)
+    R = dataset.R
+    if measured.ndim != 2 or measured.shape[0] != R:
+        raise ValueError("edc_error_bank: measured (R, Tx), one row per receiver of the dataset")
+    Ty = 2 * (dataset.z_values.shape[-1] - 1) + taps.shape[1] - 1
+    L = min(int(measured.shape[1]), Ty, int(2 * fs))
+    if L < 1:
+        raise ValueError("edc_error_bank: no samples to compare")
+    sel = _edc_rows(rows, R, dev, "edc_error_bank")
+    Dk = dataset.direct_band_render(taps, at, L)
+    Tdb = dataset.edc_error_target(measured, at, L)
+    W = bank.render_gains(dataset.norm_listener_position, R, sel)
+    if W.shape[1] <= 32:
+        Ck = bank.analysis_group_signals(dataset.z_values, taps, at, L)
+        err = ops.edc_error(Dk, Tdb, L, W=W, Ck=Ck, rows=sel, rows_checked=True)
+    else:
+        C = bank.filtered_group_signals(dataset.z_values, taps)
+        Ck = band_split(C, at, L)                                              # (S, A, L)
+        n, A = W.shape[0], at.shape[0]
+        err = torch.empty((n, A), dtype=torch.float32, device=dev)
+        for i0 in range(0, n, 128):
+            i1 = min(i0 + 128, n)
+            part = torch.arange(i0, i1, device=dev) if sel is None else sel[i0:i1]
+            Y = ops.empty_bands(i1 - i0, A, L, dev)
+            for k in range(A):
+                ops.render_mix(Dk[:, k], W[i0:i1], Ck[:, k], rows=part, out=Y[:, k])
+            ops.edc_error(Y, Tdb.index_select(0, part), L, out=err[i0:i1])
+    return err, _rmse(err)
+
+
+@torch.no_grad()
+def edc_error(estimated, measured, analysis_taps, sample_rate: float, rows=None, chunk: int = 32):
+    """The metric of ``edc_error_bank`` for ANY rendered RIRs (for instance the output of ``infer_bands``): ``estimated``
+    (R, Ty) and ``measured`` (R, Tx), tensors or numpy, ``analysis_taps`` (A, Ma), L = min(Tx, Ty, int(2 sample_rate)).
+    Both sides go through ``band_split`` (the estimate's band signals DO pass through memory here: the general path, not
+    the bank's) and the same kernel, ``chunk`` receivers at a time.  Returns (error_db (len(rows) or R, A), rmse (A,))."""
+    estimated, measured = torch.as_tensor(estimated), torch.as_tensor(measured)
+    dev = estimated.device if estimated.is_cuda else measured.device
+    if estimated.dim() != 2 or measured.dim() != 2 or estimated.shape[0] != measured.shape[0]:
+        raise ValueError("edc_error: estimated (R, Ty) and measured (R, Tx)")
+    at = torch.as_tensor(analysis_taps) if not isinstance(analysis_taps, (list, tuple)) else torch.stack(
+        [torch.as_tensor(t) for t in analysis_taps])
+    at = at.detach().to(device=dev, dtype=torch.float32).contiguous()
+    L = min(int(measured.shape[1]), int(estimated.shape[1]), int(2 * float(sample_rate)))
+    if L < 1 or at.dim() != 2:
+        raise ValueError("edc_error: no samples to compare, or analysis_taps not (A, Ma)")
+    R = estimated.shape[0]
+    sel = _edc_rows(rows, R, torch.device('cpu'), "edc_error")
+    n = R if sel is None else sel.numel()
+    err = torch.empty((n, at.shape[0]), dtype=torch.float32, device=dev)
+    for i0 in range(0, n, chunk):
+        i1 = min(i0 + chunk, n)
+        part = slice(i0, i1) if sel is None else sel[i0:i1].to(estimated.device)
+        y = estimated[part][:, :L].to(device=dev, dtype=torch.float32)
+        part = part if sel is None else part.to(measured.device)
+        x = measured[part][:, :L].to(device=dev, dtype=torch.float32)
+        Tdb = ops.edc_curve_db(band_split(x, at, L), L)
+        ops.edc_error(band_split(y, at, L), Tdb, L, out=err[i0:i1])
+    return err, _rmse(err)
+
+
 def sum_bands(local_band_rirs: Sequence[torch.Tensor], group=None, dst: int = 0, device=None) -> Optional[torch.Tensor]:
     """Sum of the filtered RIRs over ALL bands (reference :358 ``groupby('position').apply(sum)``):
     local sum over this rank's bands, then one reduce to ``dst``.  Returns the total on ``dst``,

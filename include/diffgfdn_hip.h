@@ -1036,6 +1036,22 @@ int gfdn_adam_step_mirrored(float* p, const float* g, float* m, float* v, const 
 int gfdn_render_mix(const float* d, int ld_d, const long long* rows, const float* w, const float* c, int ld_c, int R, int S,
                     int n, float* out, int ld_out, void* stream);
 
+/* ---- EDC matching error of a band bank's render  (plot.py:606-757 ``plot_edc_error_in_space`` -> ``get_edc_error`` :632-661:
+ * octave filtering, Schroeder backward integral, dB of utils.py:16-40, mean |difference| over time) for every receiver and
+ * analysis band in one pass (csrc/edcerr.hip).  With x[t] = dk[(row A + k) ld_d + t] + sum_{s < S} w[i S + s] ck[(k S + s) ld_c + t],
+ * row = rows ? rows[i] : i,  E[t] = sum_{t <= u < L} x[u]^2  and  dB(v) = max(10 log10(|v| + eps_f32), -200):
+ *     mode 0 (error):  out[i ld_o + k] = (1 / L) sum_{t < L} |dB(E[t]) - tdb[(row A + k) ld_t + t]|        (ld_o >= A)
+ *     mode 1 (curve):  out[(i A + k) ld_o + t] = dB(E[t]),  t < L        (ld_o >= L; tdb is not read: how tdb is built)
+ * i < R, k < A, float32.  dk (.., A, ld_d): the analysis-filtered part of the band signals that no parameter touches; ck (A, S,
+ * ld_c) the analysis-filtered group signals and w (R, S) the receiver gains, or S = 0 with w = ck = NULL: dk already is the
+ * band signal.  The composed signals, their squares and their EDCs stay in registers.  Tiles of 1024 samples walked
+ * backwards, float32 sums in a fixed order inside a tile, a float64 carry across tiles, no atomics: a receiver's bits do not
+ * depend on the other receivers of the launch.  S <= 32 (GFDN_E_UNSUPPORTED above).  16-byte accesses when dk, ck and tdb
+ * (mode 0) / out (mode 1) are 16-byte aligned with pitches that are multiples of 4, 4-byte accesses otherwise (the same
+ * bits); nothing is read or written behind sample L - 1 of a row; rows is not range-checked.                             */
+int gfdn_edc_err(const float* dk, int ld_d, const long long* rows, const float* w, const float* ck, int ld_c,
+                 const float* tdb, int ld_t, int R, int A, int S, int L, int mode, float* out, int ld_o, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

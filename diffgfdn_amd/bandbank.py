@@ -48,6 +48,7 @@ from .bankstep import FusedBankStep
 from .graphstep import GraphedTrainStep
 from .losses import decay_losses, edc_loss, shard_loss_scales
 from .optim import FlatAdam
+from .tensorcache import TensorCache
 
 
 class BandBank(nn.Module):
@@ -294,6 +295,9 @@ class BandStackedDataset:
         self.rir_mag_response = ds0.rir_mag_response          # shape carrier (K); targets come from the stores
         self.source_position = ds0.source_position
         self.edr_store = self.edc_store = None
+        # the constants built from the stores, each cached by the identity of its inputs (tensorcache.py)
+        self._slot_z, self._slot_cache, self._direct_time, self._direct_stft, self._edr_tiled = (TensorCache() for _ in range(5))
+        self._direct_render, self._direct_band_render, self._edc_error_target = (TensorCache(by_value=True) for _ in range(3))
         if free_sources:
             for d in datasets:
                 d.early_rir_mag_response = None
@@ -330,24 +334,22 @@ class BandStackedDataset:
     def slot_grid(self, bins: torch.Tensor, conj: torch.Tensor) -> torch.Tensor:
         """z_s (1 + S,) complex128: the frequency grid on the slot order of ``ops.irfft_slot_order`` -- column 0 = bin 0,
         column 1 + s = bin bins[s], conjugated where conj[s].  Built once, cached."""
-        if getattr(self, '_slot_z', None) is None:
-            z = self.z_values
-            self._slot_z = torch.cat([z[:1], torch.where(conj, z[bins].conj(), z[bins])])
-        return self._slot_z
+        z = self.z_values
+        return self._slot_z.get((z, bins, conj), None, lambda: torch.cat([z[:1], torch.where(conj, z[bins].conj(), z[bins])]))
 
     def slot_ordered(self, bins: torch.Tensor, conj: torch.Tensor):
         """(z_s (1 + S,) complex128, early_s (bands*R, 1 + S) complex64): the frequency grid and the early-response
         store on the slot-ordered grid (a real signal's spectrum at conj(z) is the conjugate).  Built once, cached."""
-        if getattr(self, '_slot_cache', None) is None:
-            zs = self.slot_grid(bins, conj)
-            E = self.early_rir_mag_response
+        E = self.early_rir_mag_response
+
+        def build():
             out = torch.empty((E.shape[0], 1 + bins.numel()), dtype=E.dtype, device=E.device)
             out[:, 0] = E[:, 0]
             for r0 in range(0, E.shape[0], 512):                      # bounded temporaries
                 blk = E[r0:r0 + 512][:, bins]
                 out[r0:r0 + 512, 1:] = torch.where(conj, blk.conj(), blk)
-            self._slot_cache = (zs, out)
-        return self._slot_cache
+            return self.slot_grid(bins, conj), out
+        return self._slot_cache.get((self.z_values, E, bins, conj), None, build)
 
     # the direct-path store of the linear step built with float64 transforms (csrc/fft64.hip); False: the float32 transforms
     # of csrc/fft.hip (rounds 4-5; the cross-check of tests/test_gpu_round6.py)
@@ -359,9 +361,7 @@ class BandStackedDataset:
         model.py:619, trainer.py:459, losses.py:207-213 / :442-445) that no parameter touches.  The transform is linear,
         so the step adds the band's G transformed group responses to these rows instead of transforming every receiver's
         spectrum (csrc/linear.hip).  A constant of the dataset like the decay targets: built once, cached per filter."""
-        key = (None if filt is None else (filt.data_ptr(), tuple(filt.shape)), int(n), bool(self.direct_time_f64))
-        cache = getattr(self, '_direct_time', None)
-        if cache is None or cache[0] != key:
+        def build():
             E = self.early_rir_mag_response
             R, Ku = self.R, (n + 1) // 2
             if E.shape[0] != self.num_bands * R or E.shape[1] < Ku:
@@ -389,26 +389,20 @@ class BandStackedDataset:
                     r1 = min(r0 + chunk, (q + 1) * R)
                     H = E[r0:r1, :Ku].to(torch.complex64)
                     out[r0:r1] = ops.irfft_odd_fwd((H * f) if f is not None else H.contiguous(), n)
-            self._direct_time = (key, out, filt)          # (the entry keeps the filter alive: the key is its ADDRESS, and a
-                                                          # freed filter's block handed to another one would be a false hit)
-        return self._direct_time[1]
+            return out
+        return self._direct_time.get((filt,), (int(n), bool(self.direct_time_f64)), build)
 
     def direct_render(self, taps: torch.Tensor, chunk: int = 32) -> torch.Tensor:
         """D (R, nfft + M - 1) float32: every receiver's direct path rendered through ALL bands,
         D[r] = sum_q fftconvolve(irfft(early[q R + r], n = 2 (K - 1)), taps[q], 'full') -- the part of the full-band room
         impulse responses (run_subband_training_treble.py:207-375: get_response, :321-324, :358) that no parameter
         touches; ``taps`` (bands, M) the bands' reconstructing FIRs.  A constant of the dataset and the taps like
-        ``direct_time``: built once, ``chunk`` receivers at a time, and cached per taps -- by the tensor's address, shape
-        and version (the entry keeps the tensor alive, as ``direct_time`` keeps its filter), else by value against a copy
-        of the taps the entry was built from: other taps, or the same tensor edited in place, rebuild it.  The rows'
+        ``direct_time``: built once, ``chunk`` receivers at a time, and cached per taps -- by identity, else by value
+        (tensorcache.py): other taps, or the same tensor edited in place, rebuild it.  The rows'
         pitch is a multiple of four samples (csrc/render.hip reads them 16 bytes per lane)."""
         from .subband import full_convolve
         if taps.dim() != 2 or taps.shape[0] != self.num_bands or taps.dtype != torch.float32:
             raise ValueError("direct_render: taps (bands, M) float32")
-        key = (taps.data_ptr(), tuple(taps.shape), taps._version)
-        cache = getattr(self, '_direct_render', None)
-        if cache is not None and (cache[0] == key or (cache[0][1] == key[1] and torch.equal(cache[3], taps))):
-            return cache[1]
         E = self.early_rir_mag_response
         R, K = self.R, E.shape[1]
         nfft = 2 * (K - 1)
@@ -416,52 +410,33 @@ class BandStackedDataset:
             raise RuntimeError("direct_render: the early-response store does not match bands x receivers of a power-of-two "
                                "transform")
         L = nfft + taps.shape[1] - 1
-        out = torch.zeros((R, (L + 3) // 4 * 4), dtype=torch.float32, device=E.device)[:, :L]
-        for r0 in range(0, R, chunk):
-            r1 = min(r0 + chunk, R)
-            for q in range(self.num_bands):
-                h = ops.irfft_pow2_fwd(E[q * R + r0:q * R + r1], nfft)
-                out[r0:r1] += full_convolve(h, taps[q])
-        self._direct_render = (key, out, taps, taps.detach().clone())
-        return out
+
+        def build():
+            out = torch.zeros((R, (L + 3) // 4 * 4), dtype=torch.float32, device=E.device)[:, :L]
+            for r0 in range(0, R, chunk):
+                r1 = min(r0 + chunk, R)
+                for q in range(self.num_bands):
+                    h = ops.irfft_pow2_fwd(E[q * R + r0:q * R + r1], nfft)
+                    out[r0:r1] += full_convolve(h, taps[q])
+            return out
+        return self._direct_render.get((taps,), None, build)
 
     # -- EDC matching error over the grid (subband.edc_error_bank): the dataset's two constants ------------------------
-    @staticmethod
-    def _tensor_key(t: torch.Tensor):
-        return (t.data_ptr(), tuple(t.shape), t._version)
-
-    @staticmethod
-    def _same_tensor(entry, t: torch.Tensor) -> bool:
-        """``direct_render``'s cache rule for one input: entry = (key, the tensor itself -- kept alive, its address is the
-        key --, a copy of its values): the same address, shape and version, else equal values"""
-        key = BandStackedDataset._tensor_key(t)
-        return entry[0] == key or (entry[0][1] == key[1] and entry[2].dtype == t.dtype and entry[2].device == t.device
-                                   and torch.equal(entry[2], t))
-
-    @staticmethod
-    def _tensor_entry(t: torch.Tensor):
-        return (BandStackedDataset._tensor_key(t), t, t.detach().clone())
-
     def direct_band_render(self, taps: torch.Tensor, analysis_taps: torch.Tensor, length: int) -> torch.Tensor:
         """Dk (R, A, length) float32: ``direct_render(taps)`` through every analysis band,
         Dk[r][k] = (analysis_taps[k] * D[r])[:length] (``subband.band_split``: the first ``length`` samples of the causal
         convolution) -- the part of the estimate's band signals a_k * y[r] = a_k * D[r] + sum_s W[r][s] (a_k * C_s) that no
         parameter touches (plot.py:632-661 ``get_edc_error``'s octave filtering of the estimate).  A constant of the dataset
         and both sets of taps: built once from ``direct_render(taps)`` and cached under ``direct_render``'s rule for BOTH
-        tensors (address, shape and version, else by value); other taps or analysis taps, or either edited in place,
-        rebuild it.  2.25 GB at 838 receivers x 7 bands x 96 000 samples.  The rows' pitch is a multiple of four samples."""
+        tensors; other taps or analysis taps, or either edited in place, rebuild it (the old store is dropped first: never
+        two of them alive).  2.25 GB at 838 receivers x 7 bands x 96 000 samples.  The rows' pitch is a multiple of four
+        samples."""
         from .subband import band_split
         if analysis_taps.dim() != 2 or analysis_taps.dtype != torch.float32:
             raise ValueError("direct_band_render: analysis_taps (A, Ma) float32")
         length = int(length)
-        cache = getattr(self, '_direct_band_render', None)
-        if (cache is not None and cache[0] == length and self._same_tensor(cache[2], taps)
-                and self._same_tensor(cache[3], analysis_taps)):
-            return cache[1]
-        self._direct_band_render = None                                    # (never two of them alive)
-        out = band_split(self.direct_render(taps), analysis_taps, length)
-        self._direct_band_render = (length, out, self._tensor_entry(taps), self._tensor_entry(analysis_taps))
-        return out
+        return self._direct_band_render.get((taps, analysis_taps), length,
+                                            lambda: band_split(self.direct_render(taps), analysis_taps, length))
 
     def edc_error_target(self, measured, analysis_taps: torch.Tensor, length: int, chunk: int = 32) -> torch.Tensor:
         """Tdb (R, A, length) float32: the measured side of the EDC matching error (plot.py:632-661), the EDC in dB of every
@@ -469,7 +444,7 @@ class BandStackedDataset:
         dB(v) = max(10 log10(|v| + eps_f32), -200) (utils.py:16-40) -- through the SAME kernel that scores the estimate
         (csrc/edcerr.hip, mode "curve"), ``chunk`` receivers at a time.  ``measured`` (R, T): a tensor or numpy.  Cached like
         ``direct_band_render`` per (measured, analysis_taps, length): a float32 tensor on this device is recognised by its
-        address, shape and version without a host sync; anything else is uploaded and compared by value.  2.25 GB at 838
+        identity without a host sync; anything else is uploaded and compared by value.  2.25 GB at 838
         receivers x 7 bands x 96 000 samples."""
         from .subband import band_split
         if analysis_taps.dim() != 2 or analysis_taps.dtype != torch.float32:
@@ -481,35 +456,30 @@ class BandStackedDataset:
         if m.device != dev or m.dtype != torch.float32:
             m = m.detach().to(device=dev, dtype=torch.float32)
         length = int(length)
-        cache = getattr(self, '_edc_error_target', None)
-        if (cache is not None and cache[0] == length and self._same_tensor(cache[3], analysis_taps)
-                and self._same_tensor(cache[2], m)):
-            return cache[1]
-        self._edc_error_target = None
-        out = ops.empty_bands(self.R, analysis_taps.shape[0], length, dev)
-        for r0 in range(0, self.R, chunk):
-            ops.edc_curve_db(band_split(m[r0:r0 + chunk], analysis_taps, length), length, out=out[r0:r0 + chunk])
-        self._edc_error_target = (length, out, self._tensor_entry(m), self._tensor_entry(analysis_taps))
-        return out
+
+        def build():
+            out = ops.empty_bands(self.R, analysis_taps.shape[0], length, dev)
+            for r0 in range(0, self.R, chunk):
+                ops.edc_curve_db(band_split(m[r0:r0 + chunk], analysis_taps, length), length, out=out[r0:r0 + chunk])
+            return out
+        return self._edc_error_target.get((analysis_taps, m), length, build)
 
     def edr_target_tiled(self) -> torch.Tensor:
         """The target EDR store in the tiled cell order of csrc/edrlin.hip (``ops.spec_tile``); built once, cached."""
         T = self.edr_store[1]
-        cache = getattr(self, '_edr_tiled', None)
-        if cache is None or cache[0] != (T.data_ptr(), tuple(T.shape)):
+
+        def build():
             out = torch.empty_like(T)
             for r0 in range(0, T.shape[0], 256):
                 out[r0:r0 + 256] = ops.spec_tile(T[r0:r0 + 256])
-            self._edr_tiled = ((T.data_ptr(), tuple(T.shape)), out, T)
-        return self._edr_tiled[1]
+            return out
+        return self._edr_tiled.get((T,), None, build)
 
     def direct_stft(self, filt: Optional[torch.Tensor], n: int, win: int, chunk: int = 64, tiled: bool = False) -> torch.Tensor:
         """Sd (bands*R, nframes, win / 2 + 1) complex64: the STFT (Hann ``win``, hop win / 2, as losses.py:501-553) of every
         row of ``direct_time`` -- the short-time spectrum of a receiver's signal is Sd[row] + sum_g gain_g STFT(tau_g) (the
         STFT is linear), which is what the EDR kernels of csrc/edrlin.hip compose on the fly.  Built once, cached."""
-        key = (None if filt is None else (filt.data_ptr(), tuple(filt.shape)), int(n), int(win), bool(tiled))
-        cache = getattr(self, '_direct_stft', None)
-        if cache is None or cache[0] != key:
+        def build():
             xd = self.direct_time(filt, n)
             rows = xd.shape[0]
             out = torch.empty((rows, ops.stft_nframes(n, win), win // 2 + 1), dtype=torch.complex64, device=xd.device)
@@ -520,8 +490,8 @@ class BandStackedDataset:
                     blk = torch.cat([blk, torch.zeros_like(blk[:1])])
                 x2 = torch.stack((blk[0::2], blk[1::2]), dim=-1).contiguous()
                 out[r0:r0 + m] = ops.stft_pairs_spectrum(x2, m, win, tiled=tiled)
-            self._direct_stft = (key, out, filt)
-        return self._direct_stft[1]
+            return out
+        return self._direct_stft.get((filt,), (int(n), int(win), bool(tiled)), build)
 
     def global_rows(self, per_band: Sequence[Sequence[int]]) -> List[int]:
         """per_band[q] = receiver indices of band q's batch -> band-major global rows."""
@@ -622,7 +592,7 @@ class BandBankTrainer:
             if subband_filter_freq_resp is None or subband_filter_freq_resp.shape[0] != self.num_bands:
                 raise ValueError("pass subband_filter_freq_resp as (bands, K)")
             self.subband_filter_freq_resp = subband_filter_freq_resp.to(torch.complex64).contiguous()
-        self._filt_u = None
+        self._filt_u = TensorCache()
         # Adam groups by the reference's name rules (init_scheduler :152-228)
         # (the gain network last: its range of the flat buffers can then be stepped on its own, bankstep.py)
         groups = [{'params': [bank.output_gains], 'lr': cfg.io_lr},
@@ -735,15 +705,14 @@ class BandBankTrainer:
         irfft length has one); built once."""
         if self.subband_filter_freq_resp is None:
             return None
-        if self._filt_u is None or self._filt_u[0] != (Ku, order is not None):
-            F = self.subband_filter_freq_resp
-            if order is not None:
-                bins, conj = order
-                Fu = torch.cat([F[:, :1], torch.where(conj, F[:, bins].conj(), F[:, bins])], dim=1)
-            else:
-                Fu = F[:, :Ku]
-            self._filt_u = ((Ku, order is not None), Fu.contiguous())
-        return self._filt_u[1]
+        F = self.subband_filter_freq_resp
+        bins, conj = order if order is not None else (None, None)
+
+        def build():
+            if order is None:
+                return F[:, :Ku].contiguous()
+            return torch.cat([F[:, :1], torch.where(conj, F[:, bins].conj(), F[:, bins])], dim=1).contiguous()
+        return self._filt_u.get((F, bins, conj), Ku, build)
 
     def _draw_edc_mask(self, length: int, Bper: int, device, draw_mask: bool = True, K: Optional[int] = None):
         """(maskw, 1 / (global batch x kept indices)) drawn like the reference (losses.py:221-227), the same on all

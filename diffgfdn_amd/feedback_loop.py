@@ -21,6 +21,7 @@ from torch import nn
 
 from .config import CouplingMatrixType
 from .functional import FrequencyGrid, OrthoParam, ResolventSolve, ResolventSolveFilter
+from .tensorcache import TensorCache
 
 
 class Skew(nn.Module):
@@ -156,8 +157,7 @@ class FeedbackLoop(nn.Module):
         self.coupling_matrix_order = coupling_matrix_order
         self.ortho_param = OrthoParamModule()
         self._ortho_cache = None
-        self._inv_gamma_cache = None
-        self._zp_cache = None
+        self._abs_cache, self._inv_gamma_cache, self._zp_cache = TensorCache(), TensorCache(), TensorCache()
         self._eps = 1e-9
         self._init_absorption(gains, common_decay_times)
         self._init_feedback_matrix(colorless_feedback_matrix)
@@ -180,7 +180,6 @@ class FeedbackLoop(nn.Module):
             self.delay_line_gains = torch.as_tensor(gains)
             if self.delay_line_gains.ndim not in (3, 4) or self.delay_line_gains.shape[-1] != 2:
                 raise ValueError("absorption filter coefficients: (N, S, 3, 2) SOS or (N, order, 2) IIR")
-            self._abs_cache = None
         else:
             # plain attribute like the reference (:258); moved by _apply below, and re-linked to
             # the owning model's persistent ``delay_filters`` buffer by DiffGFDN._apply
@@ -191,7 +190,7 @@ class FeedbackLoop(nn.Module):
         if not self.learn_decay_times:
             self.delay_line_gains = fn(self.delay_line_gains)
             if self.use_absorption_filters:
-                self._abs_cache = None
+                self._abs_cache.clear()
         return self
 
     def absorption_response(self, z: torch.Tensor) -> torch.Tensor:
@@ -220,11 +219,8 @@ class FeedbackLoop(nn.Module):
 
     def _inv_gamma_bins(self, z: torch.Tensor) -> torch.Tensor:
         """(K, N) complex64 = 1 / Gamma_i(z_k), cached per frequency grid (the filters are fixed)."""
-        key = (z.data_ptr(), z.numel(), z._version, str(z.device))
-        if self._abs_cache is None or self._abs_cache[0] != key:
-            G = self.absorption_response(z)
-            self._abs_cache = (key, (1.0 / G.to(torch.complex128)).to(torch.complex64).T.contiguous(), z)
-        return self._abs_cache[1]
+        return self._abs_cache.get((z,), None, lambda: (1.0 / self.absorption_response(z).to(torch.complex128))
+                                   .to(torch.complex64).T.contiguous())
 
     def current_gains(self) -> torch.Tensor:
         """gamma_n (N,), differentiable w.r.t. learnable decay times (reference :221-232)."""
@@ -354,23 +350,18 @@ class FeedbackLoop(nn.Module):
             inv_gamma = (1.0 / self.current_gains().to(dev)).to(torch.float32)
         else:
             g = self.delay_line_gains
-            key = (g.data_ptr(), g._version, str(dev))
-            if self._inv_gamma_cache is None or self._inv_gamma_cache[0] != key:
-                self._inv_gamma_cache = (key, (1.0 / g.to(dev)).to(torch.float32))
-            inv_gamma = self._inv_gamma_cache[1]
+            inv_gamma = self._inv_gamma_cache.get((g,), dev, lambda: (1.0 / g.to(dev)).to(torch.float32))
         return ResolventSolve.apply(A, inv_gamma, b.reshape(-1), grid, self.delays, transpose, None,
                                     self.precise_solve)
 
     def coupling_response(self, z: torch.Tensor, phi: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Phi(z_k) = sum_p Phi_p z_k^-p -> (K, G, G) complex64 (the frequency dependence of reference :362-373);
         the powers z_k^-p are tabulated once per grid in complex128."""
-        key = (z.data_ptr(), z.numel(), z._version, str(z.device))
-        if self._zp_cache is None or self._zp_cache[0] != key:
+        def powers():
             p = torch.arange(self.coupling_matrix_order, device=z.device, dtype=torch.float64)
-            zp = torch.exp(-p[None, :] * torch.log(z.to(torch.complex128))[:, None])
-            self._zp_cache = (key, zp.to(torch.complex64), z)
+            return torch.exp(-p[None, :] * torch.log(z.to(torch.complex128))[:, None]).to(torch.complex64)
         phi = self.construct_coupling_matrix() if phi is None else phi
-        return torch.einsum('ghp,kp->kgh', phi.to(torch.complex64), self._zp_cache[1])
+        return torch.einsum('ghp,kp->kgh', phi.to(torch.complex64), self._zp_cache.get((z,), None, powers))
 
     def _resolvent_apply_filter(self, z, grid, b, transpose):
         BM = self.construct_block_mixing_matrix()

@@ -10,6 +10,7 @@ from typing import Optional
 import torch
 
 from . import hip_ops as ops
+from .tensorcache import TensorCache
 
 
 class FrequencyGrid:
@@ -18,13 +19,10 @@ class FrequencyGrid:
     reference: dataloader.py:552-566 builds z = polar(r, 2 pi rfftfreq(nfft)); the models raise
     it to the delay lengths every forward (feedback_loop.py:330)."""
 
-    _cache = {}
-    _capacity = 64
+    _cache = TensorCache(capacity=64, no_capture="FrequencyGrid: first use of this z_values tensor inside a stream capture; "
+                                                  "run the step once before capturing it")
 
     def __init__(self, z: torch.Tensor):
-        # (the cache key is the tensor's ADDRESS and version: the entry keeps the tensor alive, so that the allocator cannot
-        # hand its block to another z of the same length while the entry exists -- a freed grid's address reused by a
-        # different grid was a false hit waiting to happen: wrong phasors, H off by 4e-3 in one test order)
         self.z = z
         self.K = z.numel()
         self.turns, logr = ops.zprep(z)
@@ -50,23 +48,14 @@ class FrequencyGrid:
 
     @classmethod
     def of(cls, z: torch.Tensor) -> "FrequencyGrid":
-        key = (z.data_ptr(), z.numel(), z._version, str(z.device))
-        g = cls._cache.get(key)
-        if g is None:
-            if torch.cuda.is_current_stream_capturing():
-                # (building a grid reads the device: a step must have met its z BEFORE it is captured -- the warm-up does)
-                raise RuntimeError("FrequencyGrid: first use of this z_values tensor inside a stream capture; run the step "
-                                   "once before capturing it")
-            # Oldest entry out, one at a time.  (The cache used to be CLEARED at nine entries: seven bands' steps, each with
-            # its own copy of z, in a process whose cache already held a few grids lost the first bands' entries during the
-            # later bands' warm-up -- and then built them again, with their host reads, inside the capture:
-            # hipErrorStreamCaptureUnsupported / ...Unjoined.)  Steps keep the grids they recorded pointers of alive
-            # themselves (GraphedModuleStep._grids).
-            while len(cls._cache) >= cls._capacity:
-                cls._cache.pop(next(iter(cls._cache)))
-            g = cls(z)
-            cls._cache[key] = g
-        return g
+        # (building a grid reads the device: a step must have met its z BEFORE it is captured -- the warm-up does)
+        return cls._cache.get((z,), None, lambda: cls(z))
+
+    @classmethod
+    def live(cls):
+        """The grids the cache holds now.  Steps keep the grids they recorded pointers of alive themselves
+        (graphstep._pinned_grids): the cache may drop them."""
+        return cls._cache.values()
 
 
 class OrthoParam(torch.autograd.Function):

@@ -42,8 +42,8 @@ def _warm_up(trainer, stream, step: Callable, also_reset: Optional[Callable] = N
 
 def _pinned_grids():
     """The recorded launches hold raw pointers into the frequency grids (turns / log radius): a step keeps the grid objects
-    alive as long as its graphs (the by-pointer cache may drop them)."""
-    return list(FrequencyGrid._cache.values())
+    alive as long as its graphs (the cache may drop them)."""
+    return FrequencyGrid.live()
 
 
 def _drain_for(*graphs):

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .tensorcache import TensorCache
 
 _c64 = torch.complex64
 _f32 = torch.float32
@@ -982,27 +983,20 @@ def tf8_param_grads(A0, ig0, part0, b, c, M, A1=None, ig1=None, part1=None, gQ=N
 
 
 # ---- the 8-line block transfer functions on the rfftfreq grid by fast transforms (csrc/polyfft.hip) ----
-_tfp_plans = {}
+_tfp_plans = TensorCache(capacity=64, no_capture="tfp_plan: first use of this delays tensor inside a stream capture; run the "
+                                                  "step once before")
 _tfp_slots = {}
 
 
 def tfp_plan(delays, nper: int, nfft: int):
     """Samples per coefficient sequence (max degree + 1, rounded up to 256, <= nfft) when every delay length is a
     non-negative integer (the reference's are: config.py:131-140), else None.  Reads the device once per delays tensor."""
-    key = (delays.data_ptr(), delays._version, delays.numel(), int(nper), int(nfft), str(delays.device))
-    if key not in _tfp_plans:
-        if delays.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("tfp_plan: first use of this delays tensor inside a stream capture; run the step once before")
+    def plan():
         d = delays.detach().to(torch.float64).cpu().reshape(-1, nper)
-        T = None
         if nfft >= 16 and nfft & (nfft - 1) == 0 and bool((d == d.round()).all()) and bool((d >= 0).all()):
-            T = int(min(nfft, ((int(d.sum(1).max().item()) + 256) // 256) * 256))
-        while len(_tfp_plans) >= 64:
-            _tfp_plans.pop(next(iter(_tfp_plans)))
-        # (the entry keeps the tensor alive: the key is its ADDRESS, and a freed tensor's block handed to another delays
-        # tensor of the same size would be a false hit -- rows too short for the new degrees)
-        _tfp_plans[key] = (T, delays)
-    return _tfp_plans[key][0]
+            return int(min(nfft, ((int(d.sum(1).max().item()) + 256) // 256) * 256))
+        return None
+    return _tfp_plans.get((delays,), (int(nper), int(nfft)), plan)
 
 
 def tfp_slot_of_bin(n: int, device):

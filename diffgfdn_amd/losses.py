@@ -26,6 +26,7 @@ from torch import nn
 
 from . import hip_ops as ops
 from .functional import IrfftPow2
+from .tensorcache import TensorCache
 
 
 def ms_to_samps(ms: float, fs: float) -> int:
@@ -86,52 +87,20 @@ def time_response_odd(X: torch.Tensor) -> torch.Tensor:
 class DecayTargets:
     """EDR / EDC of the TARGET responses, computed once and cached.
 
-    A target tensor is identified by (data_ptr, shape, version).  ``edr``: (T_db (B,frames,F),
+    A target tensor is identified as tensorcache.py says.  ``edr``: (T_db (B,frames,F),
     sum_abs (B,)); ``edc``: T_db (B, len)."""
 
     def __init__(self, max_entries: int = 64):
-        self._rir: Dict = {}
-        self._edr: Dict = {}
-        self._edc: Dict = {}
-        self.max_entries = max_entries
+        self._rir, self._edr, self._edc = (TensorCache(capacity=max_entries) for _ in range(3))
 
-    @staticmethod
-    def _key(t: torch.Tensor, *extra):
-        return (t.data_ptr(), tuple(t.shape), t._version, str(t.device)) + extra
-
-    def _trim(self, d: Dict):
-        if len(d) >= self.max_entries:
-            d.clear()
-
-    # every entry keeps a reference to its key tensor: the storage cannot be freed and re-used
-    # by another tensor while the entry is alive, so (data_ptr, version) identifies the contents
     def rir(self, target: torch.Tensor) -> torch.Tensor:
-        k = self._key(target)
-        r = self._rir.get(k)
-        if r is None:
-            self._trim(self._rir)
-            r = (time_response_odd(target), target)
-            self._rir[k] = r
-        return r[0]
+        return self._rir.get((target,), None, lambda: time_response_odd(target))
 
     def edr(self, target: torch.Tensor, win: int):
-        k = self._key(target, win)
-        e = self._edr.get(k)
-        if e is None:
-            self._trim(self._edr)
-            P = ops.stft_power(self.rir(target), win)
-            e = (ops.edr_target(P), target)
-            self._edr[k] = e
-        return e[0]
+        return self._edr.get((target,), win, lambda: ops.edr_target(ops.stft_power(self.rir(target), win)))
 
     def edc(self, target: torch.Tensor, start: int, length: int):
-        k = self._key(target, start, length)
-        e = self._edc.get(k)
-        if e is None:
-            self._trim(self._edc)
-            e = (ops.edc_target(self.rir(target), start, length), target)
-            self._edc[k] = e
-        return e[0]
+        return self._edc.get((target,), (start, length), lambda: ops.edc_target(self.rir(target), start, length))
 
     def drop_rirs(self):
         self._rir.clear()

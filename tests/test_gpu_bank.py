@@ -618,6 +618,30 @@ def test_irfft_slot_order_equals_natural_order():
     assert rel_err(torch.view_as_real(gXs).cpu(), torch.view_as_real(want).cpu()) < 1e-6
 
 
+def test_slot_ordered_store_follows_the_early_response_store():
+    """BandStackedDataset.slot_ordered is cached per (grid, early-response store, order): another store is a rebuilt
+    result, the same one the same storage.  The order here is a slot order in form only (a permutation of the bins
+    1 .. (K - 1) / 2 with conjugation flags; the 8192-point grid has none of its own): the gather does not care."""
+    from diffgfdn_amd.bandbank import BandStackedDataset
+    sds = BandStackedDataset([_build_data(q, R=5)[1] for q in range(2)])
+    half = (NFFT // 2 + 1 - 1) // 2
+    g = torch.Generator().manual_seed(11)
+    order = ((torch.randperm(half, generator=g) + 1).to(DEV), (torch.rand(half, generator=g) < 0.5).to(DEV))
+    E = sds.early_rir_mag_response
+    zs, first = sds.slot_ordered(*order)
+    want = torch.cat([E[:, :1], torch.where(order[1], E[:, order[0]].conj(), E[:, order[0]])], dim=1)
+    assert tuple(first.shape) == (2 * 5, 1 + half) and torch.equal(first, want) and float(first.abs().max()) > 0.0
+    assert torch.equal(zs, sds.slot_grid(*order))
+    sds.early_rir_mag_response = 2 * E
+    zs2, second = sds.slot_ordered(*order)
+    assert second.data_ptr() != first.data_ptr() and torch.equal(second, 2 * first), "another store: rebuilt"
+    assert torch.equal(zs2, zs)
+    sds.early_rir_mag_response = E
+    back = sds.slot_ordered(*order)[1]
+    assert torch.equal(back, first)
+    assert sds.slot_ordered(*order)[1].data_ptr() == back.data_ptr()
+
+
 def test_bank_step_slot_order_equals_natural_order_full_size():
     """nfft = 131 072 (K = 65 537, the north-star length): one bank step with the main branch evaluated on the
     irfft's slot-ordered grid against the same step on the natural grid -- losses and every gradient."""

@@ -90,6 +90,30 @@ def test_direct_path_store_is_float64_accurate(ops):
         assert np.abs(E - np.fft.rfft(early, n=nfft, axis=-1)).max() < 1e-13 * np.abs(E).max()
 
 
+def test_direct_path_store_follows_an_in_place_edit_of_the_filter(ops):
+    """direct_time is cached per filter TENSOR and its contents: the same tensor returns the same storage, the tensor
+    edited in place a new store.  Halving a filter is exact and the float64 build is linear in it, so the new rows are half
+    the old ones inside the bound above: the float32 rounding of either store, 1.2e-7 of a row's largest sample.  (Small
+    shapes: three bands of five receivers on the 8192-point grid of tests/test_gpu_bank.py; direct_stft is not reached
+    there, its transform takes windows of 4096 samples.)"""
+    from diffgfdn_amd.bandbank import BandStackedDataset
+    from tests.test_gpu_bank import BANDS, NFFT, _band_filters, _build_data
+    K = NFFT // 2 + 1
+    sds = BandStackedDataset([_build_data(q, R=5)[1] for q in range(len(BANDS))])
+    filt = torch.tensor(_band_filters(), device=DEV).to(torch.complex64)
+    xd = sds.direct_time(filt, K)
+    assert tuple(xd.shape) == (len(BANDS) * 5, K) and float(xd.abs().max()) > 0.0
+    assert sds.direct_time(filt, K).data_ptr() == xd.data_ptr()
+    filt.mul_(0.5)
+    xh = sds.direct_time(filt, K)
+    assert xh.data_ptr() != xd.data_ptr(), "a filter edited in place: a new store"
+    assert sds.direct_time(filt, K).data_ptr() == xh.data_ptr()
+    half = 0.5 * xd.double().cpu().numpy()
+    err = np.abs(xh.double().cpu().numpy() - half) / np.abs(half).max(axis=-1, keepdims=True)
+    print(f"[direct_time] after filt.mul_(0.5): largest |new - old / 2| / row top = {err.max():.3e}")
+    assert err.max() < 1.2e-7, err.max()
+
+
 # ---------------------------------------------------------------------------------------------
 # bands with their own gain networks (reference run_subband_training_treble.py:61-73)
 MIXED = [(8, 1), (16, 1), (16, 5), (128, 3)]          # (neurons, hidden layers) per band

@@ -226,6 +226,9 @@ SIGNATURES = {
     "gfdn_draw_mask_banded": (c_int, [ctypes.c_ulonglong, _P, _P, c_int, c_int, c_int, c_float, _P, _P]),
     "gfdn_render_mix": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "gfdn_edc_err": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "gfdn_stft_spectrum": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "gfdn_edr_err_work_bytes": (c_size_t, [c_int, c_int]),
+    "gfdn_edr_err": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
 }
 
 _lib = None

@@ -255,6 +255,14 @@ class BandBank(nn.Module):
         return Ck
 
     @torch.no_grad()
+    def stft_group_signals(self, z: torch.Tensor, taps: torch.Tensor, length: int, win: int) -> torch.Tensor:
+        """Sc (bands*G, T, win/2+1) complex64: the short-time spectra of ``filtered_group_signals(z, taps)[:, :length]``
+        (``hip_ops.stft_spectrum``: the reference's ``get_stft_torch``, frames-major) -- the model's side of
+        STFT(y[r]) = STFT(D[r]) + sum_s W[r][s] STFT(C_s), bands x G spectra whatever the number of receivers
+        (subband.edr_error_bank, csrc/edrerr.hip)."""
+        return ops.stft_spectrum(self.filtered_group_signals(z, taps), int(length), int(win))
+
+    @torch.no_grad()
     def render_gains(self, positions: torch.Tensor, R: int, rows: Optional[torch.Tensor] = None, chunk: int = 4096):
         """W (len(rows) or R, bands*G): column band G + g = band's gain network at the receiver, group g -- ``group_gains``
         for all receivers of all bands (``positions`` (bands*R, 3) band-major, ``rows``: receivers < R), ``chunk`` receivers
@@ -298,6 +306,7 @@ class BandStackedDataset:
         # the constants built from the stores, each cached by the identity of its inputs (tensorcache.py)
         self._slot_z, self._slot_cache, self._direct_time, self._direct_stft, self._edr_tiled = (TensorCache() for _ in range(5))
         self._direct_render, self._direct_band_render, self._edc_error_target = (TensorCache(by_value=True) for _ in range(3))
+        self._direct_render_stft, self._edr_error_target = (TensorCache(by_value=True) for _ in range(2))
         if free_sources:
             for d in datasets:
                 d.early_rir_mag_response = None
@@ -463,6 +472,52 @@ class BandStackedDataset:
                 ops.edc_curve_db(band_split(m[r0:r0 + chunk], analysis_taps, length), length, out=out[r0:r0 + chunk])
             return out
         return self._edc_error_target.get((analysis_taps, m), length, build)
+
+    # -- EDR matching error over the grid (subband.edr_error_bank): the dataset's two constants ------------------------
+    def direct_render_stft(self, taps: torch.Tensor, length: int, win: int, chunk: int = 32) -> torch.Tensor:
+        """Sd (R, T, win/2+1) complex64, frames-major: the short-time spectra of ``direct_render(taps)[:, :length]``
+        (``hip_ops.stft_spectrum``: the reference's ``get_stft_torch``, losses.py:501-553) -- the part of
+        STFT(y[r]) = STFT(D[r]) + sum_s W[r][s] STFT(C_s) that no parameter touches (plot.py:782-822 ``get_edr_error``'s
+        STFT of the estimate).  A constant of the dataset and the taps: built once from ``direct_render(taps)``, ``chunk``
+        receivers per launch straight into the store (no temporaries), and cached under ``direct_band_render``'s rule per
+        (taps, length, win): by identity, else by value; other taps, or the same tensor edited in place, rebuild it (the old
+        store is dropped first: never two of them alive).  R T (win/2+2) 8 bytes: 0.43 GB at 838 receivers, win 4096 and
+        64 000 samples (T = 31), 0.87 GB at 131 200 samples (T = 63).  The frame rows' pitch is an even number of bins."""
+        length, win = int(length), int(win)
+
+        def build():
+            D = self.direct_render(taps)
+            out = ops.empty_spectra(self.R, ops.stft_nframes(length, win), win // 2 + 1, D.device)
+            for r0 in range(0, self.R, chunk):
+                ops.stft_spectrum(D[r0:r0 + chunk], length, win, out=out[r0:r0 + chunk])
+            return out
+        return self._direct_render_stft.get((taps,), (length, win), build)
+
+    def edr_error_target(self, measured, length: int, win: int, chunk: int = 32) -> torch.Tensor:
+        """Tdb (R, T, win/2+1) float32, frames-major: the measured side of the EDR matching error (plot.py:782-822), the EDR
+        in dB of every measured RIR, dB(sum_{tau >= m} |STFT(measured[r][:length])[f][tau]|^2) with
+        dB(v) = max(10 log10(|v| + eps_f32), -200) (losses.py:556-575, utils.py:16-40) -- through the SAME kernel that
+        scores the estimate (csrc/edrerr.hip, mode "curve"), ``chunk`` receivers at a time (temporaries: the chunk's
+        spectra, chunk T (win/2+2) 8 bytes).  ``measured`` (R, Tx): a tensor or numpy.  Cached like ``direct_render_stft`` per
+        (measured, length, win): a float32 tensor on this device is recognised by its identity without a host sync;
+        anything else is uploaded and compared by value.  R T (win/2+4) 4 bytes: 0.21 GB at 838 receivers, win 4096 and
+        64 000 samples, 0.43 GB at 131 200 samples.  The frame rows' pitch is a multiple of four bins."""
+        m = torch.as_tensor(measured)
+        if m.dim() != 2 or m.shape[0] != self.R:
+            raise ValueError("edr_error_target: measured (R, T), one row per receiver")
+        dev = self.early_rir_mag_response.device
+        if m.device != dev or m.dtype != torch.float32:
+            m = m.detach().to(device=dev, dtype=torch.float32)
+        if m.stride(1) != 1:
+            m = m.contiguous()
+        length, win = int(length), int(win)
+
+        def build():
+            out = ops.empty_edr(self.R, ops.stft_nframes(length, win), win // 2 + 1, dev)
+            for r0 in range(0, self.R, chunk):
+                ops.edr_curve_db(ops.stft_spectrum(m[r0:r0 + chunk], length, win), out=out[r0:r0 + chunk])
+            return out
+        return self._edr_error_target.get((m,), (length, win), build)
 
     def edr_target_tiled(self) -> torch.Tensor:
         """The target EDR store in the tiled cell order of csrc/edrlin.hip (``ops.spec_tile``); built once, cached."""

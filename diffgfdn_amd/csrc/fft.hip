@@ -1793,3 +1793,75 @@ extern "C" int gfdn_stft_power_bwd(const float* x, int ld, int T, int batch, int
   GFDN_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------
+// The COMPLEX short-time spectrum of plain rows, frames-major: S[(b nframes + m) ld_f + f] = STFT(x[b][:L])[f][m] with the
+// window, hop and padding of gfdn_stft_power (losses.py:501-553) and its transform code -- two frames per complex FFT, the
+// Hermitian split of the epilogues above with the pair stored instead of squared.  The row holds T <= L samples; what lies
+// behind them up to the padded length of L counts as zero (x[:, :L] of a shorter row, and the zero padding itself).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(S4K_T) void k_stft4k_spectrum(const float* __restrict__ x, int ld, int T, int nframes,
+                                                           float2* __restrict__ S, int ld_f) {
+  float2* buf = dyn_lds;
+  const int b = blockIdx.y, m = blockIdx.x * 2, i = threadIdx.x;
+  float2 a[16], w1;
+  float h[16];
+  s4k_load(x + (size_t)b * ld, T, m, nframes, i, a, h, w1);
+  fft4096(a, buf, i, w1, 1.0f);
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 16; ++u) buf[S4K_PAD(i + 256 * u)] = a[u];
+  __syncthreads();
+  float2* Sa = S + ((size_t)b * nframes + m) * ld_f;
+  const bool has_b = m + 1 < nframes;
+#pragma unroll
+  for (int u = 0; u < 9; ++u) {
+    const int f = i + 256 * u;
+    if (u < 8 || i == 0) {
+      const float2 zf = a[u], zc = buf[S4K_PAD((4096 - f) & 4095)];
+      // S_a = (Z_f + conj Z_{W-f})/2 ; S_b = (Z_f - conj Z_{W-f})/(2i)
+      Sa[f] = make_float2(0.5f * (zf.x + zc.x), 0.5f * (zf.y - zc.y));
+      if (has_b) Sa[ld_f + f] = make_float2(0.5f * (zf.y + zc.y), -0.5f * (zf.x - zc.x));
+    }
+  }
+}
+
+__global__ __launch_bounds__(STFT_T) void k_stft_spectrum(const float* __restrict__ x, int ld, int T, int W, int nframes,
+                                                       float2* __restrict__ S, int ld_f) {
+  float2* bufA = dyn_lds;
+  float2* bufB = bufA + W;
+  float2* tw4 = bufB + W;
+  const int b = blockIdx.y, m = blockIdx.x * 2, nf = W / 2 + 1;
+  build_tw4(tw4, W);
+  stft_load_pair(x + (size_t)b * ld, T, W, m, nframes, bufA);
+  __syncthreads();
+  const float2* Z = lds_fft(bufA, bufB, W, 1, W, false, tw4, W);
+  float2* Sa = S + ((size_t)b * nframes + m) * ld_f;
+  const bool has_b = m + 1 < nframes;
+  for (int f = threadIdx.x; f < nf; f += blockDim.x) {
+    const float2 zf = Z[f], zc = Z[(W - f) & (W - 1)];
+    Sa[f] = make_float2(0.5f * (zf.x + zc.x), 0.5f * (zf.y - zc.y));
+    if (has_b) Sa[ld_f + f] = make_float2(0.5f * (zf.y + zc.y), -0.5f * (zf.x - zc.x));
+  }
+}
+
+extern "C" int gfdn_stft_spectrum(const float* x, int ld, int T, int L, int batch, int win, float* S_c64, int ld_f,
+                                  void* stream) {
+  if (!x || !S_c64 || batch <= 0 || T <= 0 || T > L || ld < T) return GFDN_E_BADARG;
+  const int nframes = gfdn_stft_nframes(L, win);
+  if (nframes <= 0 || ld_f < win / 2 + 1 || ((uintptr_t)S_c64 & 7)) return GFDN_E_BADARG;
+  if (batch > 65535) return GFDN_E_UNSUPPORTED;
+  if (win == 4096) {
+    hipLaunchKernelGGL(k_stft4k_spectrum, dim3((nframes + 1) / 2, batch), dim3(S4K_T), S4K_LDS * sizeof(float2),
+                       (hipStream_t)stream, x, ld, T, nframes, (float2*)S_c64, ld_f);
+    GFDN_LAUNCH_CHECK();
+    return 0;
+  }
+  if (stft_lds(win) > 160 * 1024) return GFDN_E_UNSUPPORTED;
+  int rc = ensure_dyn_lds(k_stft_spectrum, stft_lds(win));
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_stft_spectrum, dim3((nframes + 1) / 2, batch), dim3(STFT_T), stft_lds(win), (hipStream_t)stream, x,
+                     ld, T, win, nframes, (float2*)S_c64, ld_f);
+  GFDN_LAUNCH_CHECK();
+  return 0;
+}

@@ -2061,6 +2061,122 @@ def edc_curve_db(Dk, L: int, rows=None, out=None, *, rows_checked: bool = False)
     return out
 
 
+def empty_spectra(rows: int, T: int, F: int, device) -> torch.Tensor:
+    """(rows, T, F) complex64 view of frame rows whose pitch is the next even number of bins: every frame row starts on a
+    16-byte boundary (csrc/edrerr.hip)"""
+    return torch.empty((rows, T, (F + 1) // 2 * 2), dtype=_c64, device=device)[:, :, :F]
+
+
+def empty_edr(rows: int, T: int, F: int, device) -> torch.Tensor:
+    """(rows, T, F) float32 view of frame rows whose pitch is the next multiple of four bins (16-byte boundaries)"""
+    return torch.empty((rows, T, (F + 3) // 4 * 4), dtype=_f32, device=device)[:, :, :F]
+
+
+def _frame_rows(t, name: str, dtype, what: str) -> torch.Tensor:
+    """a (rows, T, F) tensor of ``dtype`` with contiguous bins and ONE pitch: stride(0) = T * stride(1)"""
+    if (t.dtype != dtype or t.dim() != 3 or t.numel() == 0 or t.stride(2) != 1 or t.stride(1) < t.shape[2]
+            or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)) or t.stride(1) >= 2 ** 30):
+        kind = "complex64" if dtype == _c64 else "float32"
+        raise RuntimeError(f"{what}: {name} must be a {kind} (rows, T, F) tensor with contiguous bins and one frame pitch")
+    return t.detach()
+
+
+def stft_spectrum(x, L: int, win: int, out=None) -> torch.Tensor:
+    """S (rows, T, win/2+1) complex64, frames-major: the short-time spectrum of x[:, :L] as the reference's
+    ``get_stft_torch`` takes it (losses.py:501-553: zero-padded to a multiple of hop = win / 2, periodic Hann, center=False,
+    one-sided, un-normalised), S[r][m][f] = torch.stft(...)[r][f][m]; T = (ceil(L / hop) hop - win) / hop + 1.  x (rows, Tx)
+    float32 with contiguous rows (a row-strided view is consumed in place); rows shorter than L count as zero behind their
+    end.  Any power-of-two ``win`` that ``stft_power`` takes, on its transform code (csrc/fft.hip).  Without ``out`` the
+    result is a view of frame rows with an even pitch (``empty_spectra``)."""
+    what = "stft_spectrum"
+    _need_gpu(x, out)
+    L, win = int(L), int(win)
+    if x.dtype != _f32 or x.dim() != 2 or x.numel() == 0 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise RuntimeError(f"{what}: x must be a float32 (rows, Tx) matrix with contiguous rows")
+    if L < 1:
+        raise RuntimeError(f"{what}: L >= 1")
+    x = x.detach()
+    nf = stft_nframes(L, win)
+    F = win // 2 + 1
+    rows = x.shape[0]
+    if out is None:
+        out = empty_spectra(rows, nf, F, x.device)
+    else:
+        out = _frame_rows(out, "out", _c64, what)
+        if tuple(out.shape) != (rows, nf, F):
+            raise RuntimeError(f"{what}: out must be (rows, {nf}, {F})")
+    lib = _lib.load()
+    for r0 in range(0, rows, 32768):
+        xs, os_ = x[r0:r0 + 32768], out[r0:r0 + 32768]
+        _lib.check(lib.gfdn_stft_spectrum(_p(xs), x.stride(0), min(L, x.shape[1]), L, xs.shape[0], win, _p(os_),
+                                          out.stride(1), _stream()), "gfdn_stft_spectrum")
+    return out
+
+
+def _edr_err_work(R: int, F: int, device) -> torch.Tensor:
+    return torch.empty(max(_lib.load().gfdn_edr_err_work_bytes(R, F) // 8, 1), dtype=torch.float64, device=device)
+
+
+def edr_error(Sd, Tdb, W=None, Sc=None, rows=None, out=None, *, rows_checked: bool = False) -> torch.Tensor:
+    """err (R,): the EDR matching error in dB of every receiver (reference plot.py:782-822 ``get_edr_error``;
+    csrc/edrerr.hip), err[i] = mean_{m, f} |dB(E[m][f]) - Tdb[row][m][f]| with s = Sd[row] + sum_s W[i][s] Sc[s],
+    E[m][f] = sum_{tau >= m} |s[tau][f]|^2, dB(v) = max(10 log10(|v| + eps_f32), -200), row = rows[i] (default i).  Sd
+    (R_store, T, F) complex64 the short-time spectra that no parameter touches (``stft_spectrum``'s layout), Tdb
+    (R_store, T, F) float32 the measured side's EDR in dB (``edr_curve_db``), W (R, S) and Sc (S, T, F) the receiver gains
+    and the group signals' spectra -- or neither: Sd already is the estimate's spectrum.  S <= 32.  The composed spectra
+    and their EDRs are never stored.  ``rows`` is range-checked here (one host sync) unless ``rows_checked``."""
+    what = "edr_error"
+    _need_gpu(Sd, Tdb, W, Sc, rows, out)
+    Sd, Tdb = _frame_rows(Sd, "Sd", _c64, what), _frame_rows(Tdb, "Tdb", _f32, what)
+    T, F = Sd.shape[1], Sd.shape[2]
+    if tuple(Tdb.shape) != tuple(Sd.shape):
+        raise RuntimeError(f"{what}: Sd and Tdb must have the same rows, frames and bins")
+    if (W is None) != (Sc is None):
+        raise RuntimeError(f"{what}: W and Sc come together")
+    S = 0
+    if W is not None:
+        W, Sc = _f(W), _frame_rows(Sc, "Sc", _c64, what)
+        if W.dim() != 2 or W.numel() == 0 or tuple(Sc.shape) != (W.shape[1], T, F):
+            raise RuntimeError(f"{what}: W (R, S) and Sc (S, T, F) expected")
+        S = W.shape[1]
+        if S > 32:
+            raise RuntimeError(f"{what}: at most 32 group signals (mix the spectra first and pass them as Sd)")
+    R = W.shape[0] if W is not None else (Sd.shape[0] if rows is None else rows.numel())
+    rows = _edc_rows(rows, R, Sd.shape[0], what, rows_checked)
+    if rows is None and Sd.shape[0] < R:
+        raise RuntimeError(f"{what}: Sd must have one row per receiver (or pass rows)")
+    if out is None:
+        out = torch.empty((R,), dtype=_f32, device=Sd.device)
+    elif out.dtype != _f32 or tuple(out.shape) != (R,) or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be a contiguous float32 (R,) tensor")
+    work = _edr_err_work(R, F, Sd.device)
+    _lib.check(_lib.load().gfdn_edr_err(_p(Sd), Sd.stride(1), _p(rows), _p(W), _p(Sc), 0 if Sc is None else Sc.stride(1),
+                                        _p(Tdb), Tdb.stride(1), R, T, F, S, 0, _p(out), 0, _p(work), _stream()),
+               "gfdn_edr_err")
+    return out
+
+
+def edr_curve_db(Sd, rows=None, out=None, *, rows_checked: bool = False) -> torch.Tensor:
+    """out (R, T, F) float32: the EDR in dB of the spectra Sd (R_store, T, F) themselves, dB(sum_{tau >= m} |Sd[row][tau][f]|^2),
+    through the arithmetic of ``edr_error`` (csrc/edrerr.hip, mode "curve": how the measured side's ``Tdb`` is built).
+    Without ``out`` the result is a view of frame rows whose pitch is a multiple of four bins (``empty_edr``)."""
+    what = "edr_curve_db"
+    _need_gpu(Sd, rows, out)
+    Sd = _frame_rows(Sd, "Sd", _c64, what)
+    T, F = Sd.shape[1], Sd.shape[2]
+    R = Sd.shape[0] if rows is None else rows.numel()
+    rows = _edc_rows(rows, R, Sd.shape[0], what, rows_checked)
+    if out is None:
+        out = empty_edr(R, T, F, Sd.device)
+    else:
+        out = _frame_rows(out, "out", _f32, what)
+        if tuple(out.shape) != (R, T, F):
+            raise RuntimeError(f"{what}: out must be (R, T, F)")
+    _lib.check(_lib.load().gfdn_edr_err(_p(Sd), Sd.stride(1), _p(rows), None, None, 0, None, 0, R, T, F, 0, 1, _p(out),
+                                        out.stride(1), None, _stream()), "gfdn_edr_err")
+    return out
+
+
 def rfft_pow2_f64(x, n: int, kout: Optional[int] = None) -> torch.Tensor:
     """x (batch, T <= n) float64 -> the first ``kout`` (default n / 2 + 1) bins of rfft(x, n) as complex128 (csrc/fft64.hip:
     float64 radix-2 passes -- dataset constants only, speed is not the point)."""

@@ -191,7 +191,8 @@ def edc_error_bank(bank, dataset, taps, measured, sample_rate: Optional[float] =
     else is uploaded and compared by value against the cached target's source).  ``sample_rate`` defaults to the bank's;
     ``rows``: receivers to score, in this order (default all R) -- a job that spreads receivers over ranks passes every rank
     its share, and the job's rmse is the root of the ranks' summed squares over the total count.  Not covered:
-    ``norm_edc=True``, position re-ordering, the plots, the EDR variant.
+    ``norm_edc=True``, position re-ordering, the plots.  The EDR variant (``plot_edr_error_in_space``) is
+    ``edr_error_bank``.
     Returns (error_db (len(rows) or R, A), rmse (A,)) float32 on the bank's device."""
     dev = bank.input_gains.device
     taps, at = _edc_taps(bank, taps, analysis_taps)
@@ -255,6 +256,107 @@ def edc_error(estimated, measured, analysis_taps, sample_rate: float, rows=None,
         x = measured[part][:, :L].to(device=dev, dtype=torch.float32)
         Tdb = ops.edc_curve_db(band_split(x, at, L), L)
         ops.edc_error(band_split(y, at, L), Tdb, L, out=err[i0:i1])
+    return err, _rmse(err)
+
+
+def _edr_frames(L: int, win_size, hop_size, what: str):
+    """(win, T) of the reference's STFT of an L-sample signal (losses.py:501-553); ValueError where it has none"""
+    win = int(win_size)
+    if hop_size is not None and int(hop_size) != win // 2:
+        raise ValueError(f"{what}: hop_size must be win_size // 2 (the reference asserts it, losses.py:524)")
+    if win < 4 or win & (win - 1):
+        raise ValueError(f"{what}: win_size must be a power of two")
+    hop = win // 2
+    padded = -(-L // hop) * hop
+    if L < 1 or padded < win:
+        raise ValueError(f"{what}: {L} samples padded to whole hops are shorter than one window of {win}: no frame")
+    return win, (padded - win) // hop + 1
+
+
+@torch.no_grad()
+def edr_error_bank(bank, dataset, taps, measured, win_size: int = 4096, hop_size: Optional[int] = None, rows=None):
+    """The EDR matching error of a trained band bank over the receiver grid in one pass: the reference's
+    ``plot_edr_error_in_space`` -> ``get_edr_error`` (plot.py:760-874, the metric at :782-822; its "RMSE in matching EDR is
+    ... dB" line) of the bank's full-band render (``infer_bank``) against the measured RIRs.
+
+        L = min(Tx, Ty)                                  (plot.py:848-852; no 2 fs clamp here, unlike the EDC metric)
+        S^x[r] = STFT(measured[r][:L]),  S^y[r] = STFT(y[r][:L])       (losses.py:501-553 ``get_stft_torch``: zero-padded to
+                 whole hops, periodic Hann of win_size, hop = win_size / 2, nfft = win_size, center=False, one-sided)
+        EDR[r][f][m] = dB(sum_{tau >= m} |S[r][f][tau]|^2),  dB(v) = max(10 log10(|v| + eps_f32), -200)
+                                                      (losses.py:556-575, utils.py:16-40: floor at about -69.2 dB)
+        error_db[r] = mean_{f, m} |EDR^x[r] - EDR^y[r]|,  rmse = ||error_db||_2 / sqrt(R)                (plot.py:818-821)
+
+    The STFT is linear, as are truncation and zero padding, so STFT(y[r][:L]) = STFT(D[r][:L]) + sum_s W[r][s] STFT(C_s[:L]):
+    ``dataset.direct_render_stft`` and ``dataset.edr_error_target`` are constants (built on the first call, cached; 0.43 GB
+    and 0.21 GB at 838 receivers, win 4096 and 64 000 samples, about twice that at 131 200), the model contributes bands x G
+    short-time spectra (``bank.stft_group_signals``), and csrc/edrerr.hip composes, squares, sums the tails and compares
+    every receiver without storing the estimate's spectra.  More than 32 group signals: the spectra are mixed with
+    ``hip_ops.render_mix`` on the float view of the complex rows into a temporary, 128 receivers at a time.
+
+    ``measured`` (R, Tx): tensor or numpy; pass a float32 device tensor for a steady state without host syncs (anything
+    else is uploaded and compared by value against the cached target's source).  ``hop_size``: None or win_size // 2 (the
+    reference asserts it).  ``rows``: receivers to score, in this order (default all R) -- a job that spreads receivers over
+    ranks passes every rank its share.  Not covered: position re-ordering (``order_position_matrices``: rows are the
+    dataset's receiver order), the plots, several sources, ERB grouping, and a job-level reduction of ``rmse`` over ranks
+    (the root of the ranks' summed squares over the total count).
+    Returns (error_db (len(rows) or R,), rmse ()) float32 on the bank's device."""
+    dev = bank.input_gains.device
+    taps, _ = _edc_taps(bank, taps, None)
+    if taps.dim() != 2 or taps.shape[0] != bank.num_bands or dataset.num_bands != bank.num_bands:
+        raise ValueError("edr_error_bank: one row of taps and one dataset per band of the bank")
+    R = dataset.R
+    if measured.ndim != 2 or measured.shape[0] != R:
+        raise ValueError("edr_error_bank: measured (R, Tx), one row per receiver of the dataset")
+    Ty = 2 * (dataset.z_values.shape[-1] - 1) + taps.shape[1] - 1
+    L = min(int(measured.shape[1]), Ty)
+    win, T = _edr_frames(L, win_size, hop_size, "edr_error_bank")
+    sel = _edc_rows(rows, R, dev, "edr_error_bank")
+    Sd = dataset.direct_render_stft(taps, L, win)
+    Tdb = dataset.edr_error_target(measured, L, win)
+    W = bank.render_gains(dataset.norm_listener_position, R, sel)
+    Sc = bank.stft_group_signals(dataset.z_values, taps, L, win)
+    if W.shape[1] <= 32:
+        err = ops.edr_error(Sd, Tdb, W=W, Sc=Sc, rows=sel, rows_checked=True)
+    else:
+        n, F = W.shape[0], win // 2 + 1
+        err = torch.empty((n,), dtype=torch.float32, device=dev)
+        # (the frame rows of both stores have ops.empty_spectra's pitch: a receiver's spectrum is one float32 row)
+        d_flat = torch.view_as_real(Sd.as_strided((R, T * Sd.stride(1)), (Sd.stride(0), 1))).flatten(1)
+        c_flat = torch.view_as_real(Sc.as_strided((Sc.shape[0], T * Sc.stride(1)), (Sc.stride(0), 1))).flatten(1)
+        for i0 in range(0, n, 128):
+            i1 = min(i0 + 128, n)
+            part = torch.arange(i0, i1, device=dev) if sel is None else sel[i0:i1]
+            Y = ops.empty_spectra(i1 - i0, T, F, dev)
+            y_flat = torch.view_as_real(Y.as_strided((i1 - i0, T * Y.stride(1)), (Y.stride(0), 1))).flatten(1)
+            ops.render_mix(d_flat, W[i0:i1], c_flat, rows=part, out=y_flat)
+            ops.edr_error(Y, Tdb.index_select(0, part), out=err[i0:i1])
+    return err, _rmse(err)
+
+
+@torch.no_grad()
+def edr_error(estimated, measured, win_size: int = 4096, rows=None, chunk: int = 32):
+    """The metric of ``edr_error_bank`` for ANY rendered RIRs (for instance the output of ``infer_bands``): ``estimated``
+    (R, Ty) and ``measured`` (R, Tx), tensors or numpy, L = min(Tx, Ty), hop = win_size // 2.  Both sides go through
+    ``hip_ops.stft_spectrum`` (the estimate's spectra DO pass through memory here: the general path, not the bank's) and
+    the same kernel with no group signals, ``chunk`` receivers at a time.  Returns (error_db (len(rows) or R,), rmse ())."""
+    estimated, measured = torch.as_tensor(estimated), torch.as_tensor(measured)
+    dev = estimated.device if estimated.is_cuda else measured.device
+    if estimated.dim() != 2 or measured.dim() != 2 or estimated.shape[0] != measured.shape[0]:
+        raise ValueError("edr_error: estimated (R, Ty) and measured (R, Tx)")
+    L = min(int(measured.shape[1]), int(estimated.shape[1]))
+    win, _ = _edr_frames(L, win_size, None, "edr_error")
+    R = estimated.shape[0]
+    sel = _edc_rows(rows, R, torch.device('cpu'), "edr_error")
+    n = R if sel is None else sel.numel()
+    err = torch.empty((n,), dtype=torch.float32, device=dev)
+    for i0 in range(0, n, chunk):
+        i1 = min(i0 + chunk, n)
+        part = slice(i0, i1) if sel is None else sel[i0:i1].to(estimated.device)
+        y = estimated[part][:, :L].to(device=dev, dtype=torch.float32).contiguous()
+        part = part if sel is None else part.to(measured.device)
+        x = measured[part][:, :L].to(device=dev, dtype=torch.float32).contiguous()
+        Tdb = ops.edr_curve_db(ops.stft_spectrum(x, L, win))
+        ops.edr_error(ops.stft_spectrum(y, L, win), Tdb, out=err[i0:i1])
     return err, _rmse(err)
 
 

@@ -818,6 +818,11 @@ int gfdn_rfft_pow2(int n, const float* x, int ld, int T, int batch, float* X_c64
 int gfdn_stft_nframes(int T, int win);
 int gfdn_stft_power(const float* x, int ld, int T, int batch, int win, float* P, float* zero_buf,
                     void* stream);
+/* the COMPLEX spectrum of the same transform for plain rows, frames-major with the bin fastest:
+ * S_c64[(b nframes + m) ld_f + f] = STFT(x[b][:L])[f][m], nframes = gfdn_stft_nframes(L, win), ld_f >= win/2+1 the pitch
+ * of a frame row in complex elements.  x: (batch, ld) float with T <= L valid samples per row: what lies behind them counts
+ * as zero (a row shorter than L, and the padding of L to a multiple of hop).  Any win gfdn_stft_power takes; batch <= 65535.  */
+int gfdn_stft_spectrum(const float* x, int ld, int T, int L, int batch, int win, float* S_c64, int ld_f, void* stream);
 /* in place: P -> EDR in dB (10 log10(sum_{tau>=m} P + eps), clipped at -200); sum_abs[b] =
  * sum |EDR| (the per-item normaliser of losses.py:487-490).                               */
 size_t gfdn_edr_work_bytes(int batch, int nfreq);
@@ -1051,6 +1056,26 @@ int gfdn_render_mix(const float* d, int ld_d, const long long* rows, const float
  * bits); nothing is read or written behind sample L - 1 of a row; rows is not range-checked.                             */
 int gfdn_edc_err(const float* dk, int ld_d, const long long* rows, const float* w, const float* ck, int ld_c,
                  const float* tdb, int ld_t, int R, int A, int S, int L, int mode, float* out, int ld_o, void* stream);
+
+/* ---- EDR matching error of a band bank's render  (plot.py:760-874 ``plot_edr_error_in_space`` -> ``get_edr_error`` :782-822:
+ * STFT of losses.py:501-553, EDR of losses.py:556-575 with the dB of utils.py:16-40, mean |difference| over frequency and
+ * time) for every receiver in one pass (csrc/edrerr.hip).  Spectra are complex64, frames-major with the bin fastest
+ * (gfdn_stft_spectrum's layout), pitches in complex elements.  With
+ *     s[m][f] = sd[(row T + m) ld_d + f] + sum_{s < S} w[i S + s] sc[(s T + m) ld_c + f],   row = rows ? rows[i] : i,
+ *     E[m][f] = sum_{m <= tau < T} |s[tau][f]|^2   and   dB(v) = max(10 log10(|v| + eps_f32), -200):
+ *     mode 0 (error):  out[i] = (1 / (T F)) sum_{m < T, f < F} |dB(E[m][f]) - tdb[(row T + m) ld_t + f]|
+ *     mode 1 (curve):  out[(i T + m) ld_o + f] = dB(E[m][f])          (ld_o >= F; tdb and work are not read: how tdb is built)
+ * i < R, float32.  sd (.., T, ld_d): the spectra that no parameter touches; sc (S, T, ld_c) the group signals' spectra and
+ * w (R, S) the receiver gains, or S = 0 with w = sc = NULL: sd already is the spectrum.  The composed spectra and their EDRs
+ * stay in registers: acc = sd, one fma per signal on the real and the imaginary part, s ascending; float32 tail sums from
+ * the last frame towards the first; |differences| added in float64 in a fixed order, no atomics: a receiver's bits depend
+ * neither on the other receivers of the launch nor on rows.  work (mode 0): gfdn_edr_err_work_bytes(R, F) bytes, 8-byte
+ * aligned.  S <= 32 (GFDN_E_UNSUPPORTED above).  8-byte accesses of the spectra when sd and sc are 8-byte aligned, 4-byte
+ * accesses otherwise (the same bits); nothing is read or written behind bin F - 1 of a row; rows is not range-checked.   */
+size_t gfdn_edr_err_work_bytes(int R, int F);
+int gfdn_edr_err(const float* sd_c64, int ld_d, const long long* rows, const float* w, const float* sc_c64, int ld_c,
+                 const float* tdb, int ld_t, int R, int T, int F, int S, int mode, float* out, int ld_o, void* work,
+                 void* stream);
 
 #ifdef __cplusplus
 }

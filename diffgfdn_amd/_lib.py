@@ -229,6 +229,9 @@ SIGNATURES = {
     "gfdn_stft_spectrum": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "gfdn_edr_err_work_bytes": (c_size_t, [c_int, c_int]),
     "gfdn_edr_err": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P]),
+    "gfdn_moving_compose": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, c_int,
+                                    _P]),
+    "gfdn_moving_ola": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

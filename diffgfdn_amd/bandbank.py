@@ -307,6 +307,7 @@ class BandStackedDataset:
         self._slot_z, self._slot_cache, self._direct_time, self._direct_stft, self._edr_tiled = (TensorCache() for _ in range(5))
         self._direct_render, self._direct_band_render, self._edc_error_target = (TensorCache(by_value=True) for _ in range(3))
         self._direct_render_stft, self._edr_error_target = (TensorCache(by_value=True) for _ in range(2))
+        self._direct_render_spectrum = TensorCache(by_value=True)
         if free_sources:
             for d in datasets:
                 d.early_rir_mag_response = None
@@ -518,6 +519,27 @@ class BandStackedDataset:
                 ops.edr_curve_db(ops.stft_spectrum(m[r0:r0 + chunk], length, win), out=out[r0:r0 + chunk])
             return out
         return self._edr_error_target.get((m,), (length, win), build)
+
+    # -- a listener moving over the grid (subband.render_moving_listener_bank): the dataset's constant -------------------
+    def direct_render_spectrum(self, taps: torch.Tensor, n: int, chunk: int = 32) -> torch.Tensor:
+        """Dh (R, n/2+1) complex64: ``rfft_pow2(direct_render(taps), n)``, the spectrum of every receiver's direct path
+        through all bands zero-padded to the power of two n >= nfft + M - 1 -- the part of
+        rfft(y[r], n) = Dh[r] + sum_s W[r][s] rfft(C_s, n) that no parameter touches (csrc/moving.hip composes the rest per
+        bin).  A constant of the dataset, the taps and n: built once from ``direct_render(taps)``, ``chunk`` receivers per
+        transform (temporaries: the chunk's rows and spectra), and cached under ``direct_render_stft``'s rule per (taps, n): by identity, else
+        by value; other taps, another n, or the same tensor edited in place, rebuild it (the old store is dropped first:
+        never two of them alive).  R (n/2+1) 8 bytes: 0.88 GB at 838 receivers and n = 2^18."""
+        n = int(n)
+
+        def build():
+            D = self.direct_render(taps)
+            if n < 16 or n & (n - 1) or n < D.shape[1]:
+                raise ValueError("direct_render_spectrum: n must be a power of two that holds a rendered row")
+            out = torch.empty((self.R, n // 2 + 1), dtype=torch.complex64, device=D.device)
+            for r0 in range(0, self.R, chunk):
+                out[r0:r0 + chunk] = ops.rfft_pow2(D[r0:r0 + chunk], n)
+            return out
+        return self._direct_render_spectrum.get((taps,), n, build)
 
     def edr_target_tiled(self) -> torch.Tensor:
         """The target EDR store in the tiled cell order of csrc/edrlin.hip (``ops.spec_tile``); built once, cached."""

@@ -2177,6 +2177,104 @@ def edr_curve_db(Sd, rows=None, out=None, *, rows_checked: bool = False) -> torc
     return out
 
 
+def _spectra_rows(t, name: str, F: int, what: str) -> torch.Tensor:
+    """a complex64 (rows, F) matrix whose rows are contiguous; a row-strided view is consumed in place"""
+    if (t.dtype != _c64 or t.dim() != 2 or t.numel() == 0 or t.shape[1] != F or t.stride(1) != 1
+            or (t.shape[0] > 1 and t.stride(0) < F) or t.stride(0) >= 2 ** 30):
+        raise RuntimeError(f"{what}: {name} must be a complex64 (rows, {F}) matrix with contiguous rows")
+    return t.detach()
+
+
+def _pitch(t) -> int:
+    """the row pitch of a matrix with contiguous rows (a single row's stride says nothing)"""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def moving_compose(Dh, Xh, ema, alpha: float, first: bool, W=None, Ch=None, rows=None, out=None, *,
+                   rows_checked: bool = False) -> torch.Tensor:
+    """Z (nseg, F) complex64: the spectra of a moving listener's filtered stimulus blocks for the segments of a chunk, in
+    order (reference sound_examples.py:163-226 ``filter_overlap_add``, :189-198; csrc/moving.hip):
+    r_k = Dh[row] + sum_s W[k][s] Ch[s], ema = r_k at the path's first segment (``first``, k = 0) and
+    alpha r_k + (1 - alpha) ema behind it, Z[k] = ema Xh[k]; row = rows[k] (default k).  Dh (R_store, F) the spectra that no
+    parameter touches, W (nseg, S) and Ch (S, F) the segments' receiver gains and the group signals' spectra -- or neither:
+    Dh already holds the RIRs' spectra.  Xh (nseg, F): spectra of the stimulus blocks.  ``ema`` (F,) complex64 contiguous:
+    the filter state, updated in place (read unless ``first``).  S <= 32.  Neither the composed RIRs nor the interpolated
+    filters are stored.  ``rows`` is range-checked here (one host sync) unless ``rows_checked``."""
+    what = "moving_compose"
+    _need_gpu(Dh, Xh, ema, W, Ch, rows, out)
+    if Xh.dim() != 2:
+        raise RuntimeError(f"{what}: Xh (nseg, F) expected")
+    nseg, F = Xh.shape
+    Dh, Xh = _spectra_rows(Dh, "Dh", F, what), _spectra_rows(Xh, "Xh", F, what)
+    if ema.dtype != _c64 or tuple(ema.shape) != (F,) or not ema.is_contiguous():
+        raise RuntimeError(f"{what}: ema must be a contiguous complex64 ({F},) vector")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise RuntimeError(f"{what}: 0 <= alpha <= 1")
+    if (W is None) != (Ch is None):
+        raise RuntimeError(f"{what}: W and Ch come together")
+    S = 0
+    if W is not None:
+        W = _f(W)
+        if W.dim() != 2 or W.shape[0] != nseg or W.shape[1] == 0:
+            raise RuntimeError(f"{what}: W (nseg, S) expected")
+        S = W.shape[1]
+        if S > 32:
+            raise RuntimeError(f"{what}: at most 32 group signals (render the RIRs and pass their spectra as Dh)")
+        Ch = _spectra_rows(Ch, "Ch", F, what)
+        if Ch.shape[0] != S:
+            raise RuntimeError(f"{what}: Ch (S, F) expected")
+    rows = _edc_rows(rows, nseg, Dh.shape[0], what, rows_checked)
+    if rows is None and Dh.shape[0] < nseg:
+        raise RuntimeError(f"{what}: Dh must have one row per segment (or pass rows)")
+    if out is None:
+        out = torch.empty((nseg, F), dtype=_c64, device=Xh.device)
+    else:
+        out = _spectra_rows(out, "out", F, what)
+        if out.shape[0] != nseg:
+            raise RuntimeError(f"{what}: out must be (nseg, F)")
+    _lib.check(_lib.load().gfdn_moving_compose(_p(Dh), _pitch(Dh), _p(rows), _p(W), _p(Ch), 0 if Ch is None else _pitch(Ch),
+                                               _p(Xh), _pitch(Xh), nseg, F, S, float(alpha), int(bool(first)), _p(ema),
+                                               _p(out), _pitch(out), _stream()), "gfdn_moving_compose")
+    return out
+
+
+def moving_ola(s, k0: int, P: int, h: int, Lr: int, Fd: int, out, tail_in, tail_out) -> torch.Tensor:
+    """Overlap-add the time-domain segments ``s`` (nseg, >= h + Lr - 1) of a chunk -- segments k0 .. k0 + nseg - 1 of a path
+    of P -- into ``out`` (P h,) float32 with the reference's linear cross-fade (sound_examples.py:199-224; csrc/moving.hip):
+    segment k covers out[k h : k h + min(h + Lr - 1, P h - k h)]; for k >= 1 its first Fd samples enter as
+    t_{k-1} fade_out + s_k fade_in, t_{k-1} the last Fd samples of the cut segment before (``tail_in`` (Fd,) for the chunk's
+    first segment, k0 > 0).  ``tail_out`` (Fd,), another buffer, receives this chunk's tail.  ``out`` is zeroed by the caller
+    before the first chunk.  Gather form: chunks, and repeats, give the same bits.  1 <= Fd <= h."""
+    what = "moving_ola"
+    _need_gpu(s, out, tail_in, tail_out)
+    k0, P, h, Lr, Fd = int(k0), int(P), int(h), int(Lr), int(Fd)
+    if h < 1 or P < 1 or Lr < 1 or not 1 <= Fd <= h:
+        raise RuntimeError(f"{what}: h >= 1, P >= 1, Lr >= 1 and 1 <= Fd <= h")
+    lfull = h + Lr - 1
+    if (s.dtype != _f32 or s.dim() != 2 or s.numel() == 0 or s.shape[1] < lfull or s.stride(1) != 1
+            or (s.shape[0] > 1 and s.stride(0) < s.shape[1]) or s.stride(0) >= 2 ** 31):
+        raise RuntimeError(f"{what}: s must be a float32 matrix with contiguous rows of at least {lfull} samples")
+    s = s.detach()
+    nseg = s.shape[0]
+    if k0 < 0 or k0 + nseg > P or P * h >= 2 ** 31:
+        raise RuntimeError(f"{what}: segments k0 .. k0 + nseg - 1 of a path of P, with P h < 2^31")
+    if out.dtype != _f32 or tuple(out.shape) != (P * h,) or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be a contiguous float32 ({P * h},) vector")
+    for t, name in ((tail_in, "tail_in"), (tail_out, "tail_out")):
+        if t is not None and (t.dtype != _f32 or tuple(t.shape) != (Fd,) or not t.is_contiguous()):
+            raise RuntimeError(f"{what}: {name} must be a contiguous float32 ({Fd},) vector")
+    if tail_out is None or (k0 > 0 and tail_in is None) or (tail_in is not None and tail_in.data_ptr() == tail_out.data_ptr()):
+        raise RuntimeError(f"{what}: tail_out, and tail_in behind the path's first chunk, as two buffers")
+    ld = _pitch(s)
+    # the 16-byte form reads a row up to the next multiple of four behind h + Lr - 1: the storage must hold that
+    room = s.untyped_storage().nbytes() // 4 - s.storage_offset() - (nseg - 1) * ld
+    if ld % 4 == 0 and h % 4 == 0 and room < (lfull + 3) // 4 * 4:
+        raise RuntimeError(f"{what}: the storage of s ends inside the last row's pitch")
+    _lib.check(_lib.load().gfdn_moving_ola(_p(s), ld, nseg, k0, P, h, Lr, Fd, _p(tail_in), _p(tail_out), _p(out), _stream()),
+               "gfdn_moving_ola")
+    return out
+
+
 def rfft_pow2_f64(x, n: int, kout: Optional[int] = None) -> torch.Tensor:
     """x (batch, T <= n) float64 -> the first ``kout`` (default n / 2 + 1) bins of rfft(x, n) as complex128 (csrc/fft64.hip:
     float64 radix-2 passes -- dataset constants only, speed is not the point)."""

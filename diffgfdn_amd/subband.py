@@ -360,6 +360,142 @@ def edr_error(estimated, measured, win_size: int = 4096, rows=None, chunk: int =
     return err, _rmse(err)
 
 
+def _moving_plan(P: int, Lr: int, fs: float, update_ms: float, alpha: float, fade_len_ms: float, what: str):
+    """(h, Fd, n) of the reference's moving-listener render; ValueError outside the declared scope"""
+    h, Fd = int(update_ms * 1e-3 * fs), int(fade_len_ms * 1e-3 * fs)        # utils.py:62-80 ``ms_to_samps``: truncation
+    if P < 1:
+        raise ValueError(f"{what}: an empty path")
+    if h < 1:
+        raise ValueError(f"{what}: update_ms is shorter than one sample")
+    if not 1 <= Fd <= h:
+        raise ValueError(f"{what}: the cross-fade must be 1 .. {h} samples (one update interval) long, not {Fd}: at 0 the "
+                         "reference raises, above one interval it fades with stale samples")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"{what}: 0 <= alpha <= 1")
+    if P * h >= 2 ** 31:
+        raise ValueError(f"{what}: P h < 2^31 samples")
+    return h, Fd, max(16, 1 << (h + Lr - 2).bit_length())
+
+
+def _moving_stimulus(stimulus, total: int, dev, what: str) -> torch.Tensor:
+    """sound_examples.py:149-161 ``create_extended_stimulus``: float32, repeated or cut to ``total`` samples"""
+    x = torch.as_tensor(stimulus).detach().to(device=dev, dtype=torch.float32).reshape(-1)
+    if x.numel() == 0:
+        raise ValueError(f"{what}: an empty stimulus")
+    return x.repeat(-(-total // x.numel()))[:total].contiguous()
+
+
+def _moving_out(out, total: int, dev, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.zeros((total,), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (total,) or not out.is_contiguous() or out.device != torch.device(dev):
+        raise ValueError(f"{what}: out must be a contiguous float32 ({total},) vector on the device")
+    return out.zero_()
+
+
+def _moving_run(x, P: int, h: int, Fd: int, Lr: int, n: int, alpha: float, chunk: int, out, chunk_inputs):
+    """compose -> inverse transform -> overlap-add, ``chunk`` segments at a time.  ``chunk_inputs(k0, k1)`` returns
+    moving_compose's (Dh, rows, W, Ch) for the segments k0 .. k1 - 1."""
+    dev = x.device
+    blocks = x.view(P, h)
+    ema = torch.empty((n // 2 + 1,), dtype=torch.complex64, device=dev)
+    tails = [torch.empty((Fd,), dtype=torch.float32, device=dev) for _ in range(2)]
+    for i, k0 in enumerate(range(0, P, chunk)):
+        k1 = min(k0 + chunk, P)
+        Dh, rows, W, Ch = chunk_inputs(k0, k1)
+        Z = ops.moving_compose(Dh, ops.rfft_pow2(blocks[k0:k1], n), ema, alpha, k0 == 0, W=W, Ch=Ch, rows=rows,
+                               rows_checked=True)
+        ops.moving_ola(ops.irfft_pow2_fwd(Z, n), k0, P, h, Lr, Fd, out, tails[i & 1] if k0 else None, tails[1 - (i & 1)])
+    return out
+
+
+@torch.no_grad()
+def render_moving_listener_bank(bank, dataset, taps, path, stimulus, update_ms: float = 100.0, alpha: float = 0.5,
+                                fade_len_ms: float = 50.0, sample_rate: Optional[float] = None, chunk: int = 32,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A dry stimulus heard by a listener who moves over the receiver grid of a trained band bank, in one pass: the
+    reference's ``dynamic_rendering_moving_receiver.filter_overlap_add`` (sound_examples.py:163-226, ``use_whole_rir=True``)
+    on the bank's full-band render (``infer_bank``) of the dataset rows ``path``, one row per update interval.
+
+        h = int(update_ms 1e-3 fs),  Fd = int(fade_len_ms 1e-3 fs),  total = P h                   (utils.py:62-80; :102, :169)
+        x = the stimulus as float32, repeated or cut to total samples,  x_k = x[k h : (k + 1) h]             (:149-161, :195)
+        f_0 = r_0,  f_k = alpha r_k + (1 - alpha) f_{k-1},  r_k = y[path[k]]   (:184-193: the recursion runs on the FILTER)
+        s_k = fftconvolve(x_k, f_k, 'full')[: min(h + Lr - 1, total - k h)]                                      (:196-203)
+        out[k h + i] += s_k[i];  for k >= 1 and i < Fd instead  t_{k-1}[i] fade_out[i] + s_k[i] fade_in[i]       (:205-217)
+        fade_in = 0.5 (1 + linspace(-1, 1, Fd)),  fade_out = 1 - fade_in,  t_{k-1} = the LAST Fd samples of s_{k-1}
+                                                                                                       (:118-127, :219-224)
+
+    Transform, interpolation and the bank's composition are linear, so with n the power of two >= h + Lr - 1 the spectrum of
+    f_k is the running average of Dh[path[k]] + sum_s W[k][s] Ch[s]: ``dataset.direct_render_spectrum(taps, n)`` is a
+    constant (built on the first call, cached; 0.88 GB at 838 receivers and n = 2^18), the model contributes bands x G
+    spectra (``rfft_pow2(bank.filtered_group_signals(...), n)``) and the gains ``bank.render_gains(..., path)``, and
+    csrc/moving.hip composes, interpolates and multiplies per bin, then overlap-adds the inverse transforms
+    (``irfft_pow2_fwd``), ``chunk`` segments at a time: neither the composed RIRs nor the interpolated filters are stored.
+    More than 32 group signals: the rows are rendered with ``infer_bank(rows=path)`` and go through
+    ``render_moving_listener``.
+
+    ``path``: P dataset rows, repeats and any order allowed; ``stimulus``: 1-D, tensor or numpy; ``sample_rate`` defaults
+    to the bank's; ``out``: a contiguous float32 (P h,) buffer to fill.  Scope: P >= 1, h >= 1 and 1 <= Fd <= h (at Fd = 0
+    the reference raises, above h its tail buffer keeps stale samples: ValueError here), 0 <= alpha <= 1.  Every call
+    starts fresh: the ``prev_filter`` that the reference leaves on its object between calls is not reproduced.  Not covered:
+    the late-RIR variant (pass late RIRs to ``render_moving_listener``), binaural / HRTF rendering, loudness
+    normalisation, the animation, wav export.
+    Returns (P h,) float32 on the bank's device."""
+    what = "render_moving_listener_bank"
+    dev = bank.input_gains.device
+    taps, _ = _edc_taps(bank, taps, None)
+    if taps.dim() != 2 or taps.shape[0] != bank.num_bands or dataset.num_bands != bank.num_bands:
+        raise ValueError(f"{what}: one row of taps and one dataset per band of the bank")
+    if path is None or torch.as_tensor(path).numel() == 0:
+        raise ValueError(f"{what}: an empty path")
+    sel = _edc_rows(path, dataset.R, dev, what)
+    P = sel.numel()
+    fs = float(bank.sample_rate if sample_rate is None else sample_rate)
+    Lr = 2 * (dataset.z_values.shape[-1] - 1) + taps.shape[1] - 1
+    h, Fd, n = _moving_plan(P, Lr, fs, update_ms, alpha, fade_len_ms, what)
+    if bank.num_bands * bank.num_groups > 32:
+        y = infer_bank(bank, dataset, taps, rows=sel)
+        return render_moving_listener(y, None, stimulus, fs, update_ms, alpha, fade_len_ms, chunk, out)
+    x = _moving_stimulus(stimulus, P * h, dev, what)
+    out = _moving_out(out, P * h, dev, what)
+    Dh = dataset.direct_render_spectrum(taps, n)
+    W = bank.render_gains(dataset.norm_listener_position, dataset.R, sel)
+    Ch = ops.rfft_pow2(bank.filtered_group_signals(dataset.z_values, taps), n)
+    return _moving_run(x, P, h, Fd, Lr, n, float(alpha), int(chunk), out,
+                       lambda k0, k1: (Dh, sel[k0:k1], W[k0:k1], Ch))
+
+
+@torch.no_grad()
+def render_moving_listener(rirs, path, stimulus, fs: float, update_ms: float = 100.0, alpha: float = 0.5,
+                           fade_len_ms: float = 50.0, chunk: int = 32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The render of ``render_moving_listener_bank`` for ANY RIR matrix (for instance the output of ``infer_bands``, or the
+    late RIRs of a dataset: the reference's ``use_whole_rir=False``): ``rirs`` (R, Lr) tensor or numpy, ``path``: P of its
+    rows (None: every row in order), ``stimulus`` 1-D, ``fs`` the sample rate.  The rows' spectra DO pass through memory
+    here, ``chunk`` segments at a time (the general path, not the bank's), into the same kernels with no group signals.
+    Returns (P h,) float32 on the device of ``rirs`` (a host matrix: on the current device)."""
+    what = "render_moving_listener"
+    rirs = torch.as_tensor(rirs)
+    if rirs.dim() != 2 or rirs.shape[1] < 1:
+        raise ValueError(f"{what}: rirs (R, Lr)")
+    dev = rirs.device if rirs.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if path is None:
+        sel = torch.arange(rirs.shape[0])
+    else:
+        if torch.as_tensor(path).numel() == 0:
+            raise ValueError(f"{what}: an empty path")
+        sel = _edc_rows(path, rirs.shape[0], torch.device("cpu"), what)
+    sel = sel.to(rirs.device)
+    P, Lr = sel.numel(), int(rirs.shape[1])
+    h, Fd, n = _moving_plan(P, Lr, float(fs), update_ms, alpha, fade_len_ms, what)
+    x = _moving_stimulus(stimulus, P * h, dev, what)
+    out = _moving_out(out, P * h, dev, what)
+
+    def chunk_inputs(k0, k1):
+        r = rirs[sel[k0:k1]].to(device=dev, dtype=torch.float32)
+        return ops.rfft_pow2(r, n), None, None, None
+    return _moving_run(x, P, h, Fd, Lr, n, float(alpha), int(chunk), out, chunk_inputs)
+
+
 def sum_bands(local_band_rirs: Sequence[torch.Tensor], group=None, dst: int = 0, device=None) -> Optional[torch.Tensor]:
     """Sum of the filtered RIRs over ALL bands (reference :358 ``groupby('position').apply(sum)``):
     local sum over this rank's bands, then one reduce to ``dst``.  Returns the total on ``dst``,

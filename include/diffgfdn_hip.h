@@ -1077,6 +1077,33 @@ int gfdn_edr_err(const float* sd_c64, int ld_d, const long long* rows, const flo
                  const float* tdb, int ld_t, int R, int T, int F, int S, int mode, float* out, int ld_o, void* work,
                  void* stream);
 
+/* ---- a listener moving through a render  (sound_examples.py:163-226 ``dynamic_rendering_moving_receiver.filter_overlap_add``:
+ * per update interval of h samples the position's RIR interpolated with the previous FILTER, f_0 = r_0,
+ * f_k = alpha r_k + (1 - alpha) f_{k-1}; s_k = fftconvolve(x_k, f_k, 'full') cut at the end of the output; overlap-add with a
+ * linear cross-fade over the first Fd samples of every segment but the first) in two launches around an inverse transform
+ * (csrc/moving.hip).  n = 2^p >= h + Lr - 1, F = n / 2 + 1; spectra complex64, pitches in complex elements.
+ *   gfdn_moving_compose: for the nseg segments of a chunk IN ORDER, per bin f < F:
+ *         r = dh[(rows ? rows[k] : k) ld_d + f] + sum_{s < S} w[k S + s] ch[s ld_c + f]         (one fma per signal and part)
+ *         ema = first && k == 0 ? r : fma(alpha, r, (1 - alpha) ema);      z[k ld_z + f] = ema xh[k ld_x + f]
+ *     dh: spectra of the rows that no parameter touches, ch (S, ld_c) and w (nseg, S) the group signals' spectra and the
+ *     segments' gains, or S = 0 with w = ch = NULL: dh already holds the RIRs' spectra.  xh (nseg, ld_x): spectra of the
+ *     stimulus blocks.  ema (F): the filter state, read unless ``first`` and written at the end -- a path in chunks gives the
+ *     bits of one launch.  0 <= alpha <= 1; S <= 32 (GFDN_E_UNSUPPORTED above); all bases 8-byte aligned; nothing is read or
+ *     written behind bin F - 1 of a row; rows is not range-checked.
+ *   gfdn_moving_ola: s (nseg, ld_s >= h + Lr - 1) the time-domain segments k0 .. k0 + nseg - 1 of a path of P; segment k
+ *     covers out[k h .. k h + len_k), len_k = min(h + Lr - 1, P h - k h).  Every covered sample of out (P h floats, zeroed
+ *     by the caller before the first chunk) takes one running sum from its value on, k ascending:
+ *         i >= Fd or k == 0:  + s_k[i]        else:  + t_{k-1}[i] (1 - i / (Fd - 1)) + s_k[i] (i / (Fd - 1))       (Fd = 1: t)
+ *     t_{k-1} = the last Fd samples of the cut segment k - 1: row k - 1 - k0 of s, or tail_in (Fd) for k = k0 > 0;
+ *     tail_out (Fd) receives the tail of segment k0 + nseg - 1 and must not be tail_in.  Gather form, no atomics: chunks
+ *     give the bits of one launch.  1 <= Fd <= h.  16-byte accesses when s and out are 16-byte aligned and ld_s and h are
+ *     multiples of 4 (s is then read up to the next multiple of 4 behind h + Lr - 1 of a row), 4-byte accesses otherwise. */
+int gfdn_moving_compose(const float* dh_c64, int ld_d, const long long* rows, const float* w, const float* ch_c64, int ld_c,
+                        const float* xh_c64, int ld_x, int nseg, int F, int S, float alpha, int first, float* ema_c64,
+                        float* z_c64, int ld_z, void* stream);
+int gfdn_moving_ola(const float* s, int ld_s, int nseg, int k0, int P, int h, int Lr, int Fd, const float* tail_in,
+                    float* tail_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

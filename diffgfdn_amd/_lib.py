@@ -93,7 +93,7 @@ SIGNATURES = {
     "gfdn_tf_compose_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P,
                                     c_int, _P]),
     "gfdn_tf_tail": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                             _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P, _P]),
+                             _P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, _P]),
     "gfdn_irfft_odd_pairs_bwd_tslots3": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, c_int, _P, _P]),
     "gfdn_irfft_odd_pairs_fwd_scaled": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, _P, c_int, _P]),
     "gfdn_edc_lin_one_max_len": (c_int, []),
@@ -128,7 +128,7 @@ SIGNATURES = {
     "gfdn_tfp_compose_bwd": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P, _P, c_int, c_int,
                                      _P, c_int, _P, c_int, _P, _P, _P]),
     "gfdn_tf8_tail": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                              _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P, _P, _P]),
+                              _P, _P, _P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P]),
     "gfdn_tf9_coefs": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     "gfdn_tf9_rec_grads_work_bytes": (c_size_t, [c_int]),
     "gfdn_tf9_rec_grads": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
@@ -193,9 +193,9 @@ SIGNATURES = {
     "gfdn_mlp_gains_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
     "gfdn_mlp_gains_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gfdn_pick_rows": (c_int, [_P, _P, _P, c_int, _P]),
-    "gfdn_adam_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_float, c_float, c_float, _P]),
-    "gfdn_adam_step_counted": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_float, c_float, c_float, _P, _P]),
-    "gfdn_adam_step_mirrored": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_float, c_float, c_float, _P, _P]),
+    "gfdn_adam_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_double, c_double, c_double, _P]),
+    "gfdn_adam_step_counted": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_double, c_double, c_double, _P, _P]),
+    "gfdn_adam_step_mirrored": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_double, c_double, c_double, _P, _P]),
     "gfdn_edc_loss": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P, _P]),
     "gfdn_edc_loss_model": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, c_float, c_float, _P, _P, _P, _P]),
     "gfdn_draw_mask": (c_int, [ctypes.c_ulonglong, _P, c_int, c_float, _P, _P]),

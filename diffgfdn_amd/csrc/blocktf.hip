@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void k_tf_tail(TfBwdSet s0, TfBwdSet s1, int n
   TFT_STAMP(3);
   // ---- Adam on the block's own entries: every element is updated by the thread that wrote its gradient
   // (tf_coefs_bwd_block: dL/db[i] by thread 32 + i, dL/dc[j] by thread 48 + j; ortho_bwd_group: dL/dM[e] by thread e)
-  const float bc1 = 1.0f - powf(ad.b1, t), bc2_sqrt = sqrtf(1.0f - powf(ad.b2, t));
+  const float bc1 = adam_bias_corr(ad.k.lb1, t), bc2_sqrt = sqrtf(adam_bias_corr(ad.k.lb2, t));
   if (tid < n * n) sM[tid] = tf_adam_elem(ad, ad.offM + (int)off + tid, gM[off + tid], bc1, bc2_sqrt);
   if (tid >= 32 && tid < 32 + n) sb[tid - 32] = tf_adam_elem(ad, ad.offb + blk * n + tid - 32, gb[blk * n + tid - 32], bc1, bc2_sqrt);
   if (tid >= 48 && tid < 48 + n) sc[tid - 48] = tf_adam_elem(ad, ad.offc + blk * n + tid - 48, gc[blk * n + tid - 48], bc1, bc2_sqrt);
@@ -537,7 +537,7 @@ extern "C" int gfdn_tf_tail(const float* A0, const float* inv_gamma0, const floa
                             const float* grec1, const float* b, const float* c, int nblk, int nper, const float* M,
                             const float* gQ, const float* Q, float* gb, float* gc, float* gM, float* flat_p, float* flat_m,
                             float* flat_v, const unsigned char* seg, const float* lr_seg, float* step_count,
-                            unsigned int* block_counter, int offM, int offb, int offc, float beta1, float beta2, float eps,
+                            unsigned int* block_counter, int offM, int offb, int offc, double beta1, double beta2, double eps,
                             float* Q_next, float* QQ_next, float* coef_next, float* coef_sub_next, void* stream) {
   if (!A0 || !grec0 || !A1 || !grec1 || !b || !c || !M || !gM || !gb || !gc || !flat_p || !flat_m || !flat_v || !seg ||
       !lr_seg || !step_count || !block_counter || !Q_next || !QQ_next || !coef_next || !coef_sub_next || nblk <= 0 ||
@@ -546,7 +546,7 @@ extern "C" int gfdn_tf_tail(const float* A0, const float* inv_gamma0, const floa
   if (nper > 4) return GFDN_E_UNSUPPORTED;
   TfBwdSet s0{A0, inv_gamma0, grec0, nullptr};
   TfBwdSet s1{A1, nullptr, grec1, nullptr};
-  TfAdam ad{flat_p, flat_m, flat_v, seg, lr_seg, step_count, block_counter, offM, offb, offc, beta1, beta2, eps};
+  TfAdam ad{flat_p, flat_m, flat_v, seg, lr_seg, step_count, block_counter, offM, offb, offc, adam_consts(beta1, beta2, eps)};
   size_t lds = ortho_bwd_lds_doubles(nper);
   const size_t lds_head = expm_lds_doubles(nper);
   if (lds_head > lds) lds = lds_head;

@@ -822,7 +822,7 @@ __global__ __launch_bounds__(256) void k_tf8_tail(const float* __restrict__ part
   __syncthreads();
   const size_t off = (size_t)blk * n * n;
   ortho_bwd_group(t8p_lds, M + off, n, gQ ? gQ + off : nullptr, sG[0], Q ? Q + off : nullptr, sG[1], gM + off);
-  const float bc1 = 1.0f - powf(ad.b1, t), bc2_sqrt = sqrtf(1.0f - powf(ad.b2, t));
+  const float bc1 = adam_bias_corr(ad.k.lb1, t), bc2_sqrt = sqrtf(adam_bias_corr(ad.k.lb2, t));
   if (tid < n * n) sM[tid] = tf_adam_elem(ad, ad.offM + (int)off + tid, gM[off + tid], bc1, bc2_sqrt);
   if (tid >= 128 && tid < 128 + n) tf_adam_elem(ad, ad.offb + blk * n + tid - 128, gb[blk * n + tid - 128], bc1, bc2_sqrt);
   if (tid >= 192 && tid < 192 + n)
@@ -882,8 +882,8 @@ extern "C" int gfdn_tf8_tail(const float* A0, const float* inv_gamma0, const flo
                              const float* part1, int nparts1, const float* b, const float* c, int nblk, int nper,
                              const float* M, const float* gQ, const float* Q, float* gb, float* gc, float* gM, void* work,
                              float* flat_p, float* flat_m, float* flat_v, const unsigned char* seg, const float* lr_seg,
-                             float* step_count, unsigned int* block_counter, int offM, int offb, int offc, float beta1,
-                             float beta2, float eps, float* Q_next, float* QQ_next, float* c_next, void* stream) {
+                             float* step_count, unsigned int* block_counter, int offM, int offb, int offc, double beta1,
+                             double beta2, double eps, float* Q_next, float* QQ_next, float* c_next, void* stream) {
   if (!A0 || !part0 || !A1 || !part1 || !b || !c || !M || !gb || !gc || !gM || !work || !flat_p || !flat_m || !flat_v || !seg ||
       !lr_seg || !step_count || !block_counter || !Q_next || !QQ_next || !c_next || nblk <= 0 || nper <= 0 || nparts0 <= 0 ||
       nparts1 <= 0 || offM < 0 || offb < 0 || offc < 0)
@@ -895,7 +895,7 @@ extern "C" int gfdn_tf8_tail(const float* A0, const float* inv_gamma0, const flo
   hipLaunchKernelGGL(k_tf8_rec_grads, dim3(nblk, 2, 2), dim3(256), 0, s, A0, inv_gamma0, part0, nparts0, A1,
                      (const float*)nullptr, part1, nparts1, b, c, nper, out0, out1);
   GFDN_LAUNCH_CHECK();
-  TfAdam ad{flat_p, flat_m, flat_v, seg, lr_seg, step_count, block_counter, offM, offb, offc, beta1, beta2, eps};
+  TfAdam ad{flat_p, flat_m, flat_v, seg, lr_seg, step_count, block_counter, offM, offb, offc, adam_consts(beta1, beta2, eps)};
   const size_t lds = ortho_bwd_lds_doubles(nper) * sizeof(double);
   int rc = ensure_dyn_lds(k_tf8_tail, lds);
   if (rc) return rc;

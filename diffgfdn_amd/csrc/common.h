@@ -1,6 +1,7 @@
 // Shared device helpers for the gfx950 kernels of the DiffGFDN hot path.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <mutex>
 #include <stddef.h>
 #include <stdint.h>
@@ -39,13 +40,34 @@ __device__ __forceinline__ float db_pow(float x) {
 
 // One element of the Adam update (torch.optim.Adam without amsgrad / weight decay; reference trainer.py:475) with every
 // rounding pinned -- two kernels step ranges of one flat buffer (optim.hip k_adam, blocktf.hip k_tf_tail) and must agree
-// to the bit whatever the compiler would contract:  m <- m + (g - m)(1 - b1);  v <- v b2 + g g (1 - b2);
+// to the bit whatever the compiler would contract:  m <- m + (g - m)(1 - b1);  v <- v b2 + g g (1 - b2) (in double);
 // p <- p - (lr / bc1) m / (sqrt(v) / bc2_sqrt + eps).  Returns the new parameter.
+// The constants come from the DOUBLE betas the optimiser holds (AdamConsts below), as torch forms them: 1 - b rounded once
+// from the double difference.  Formed in float from the rounded betas they are 1 - 0.9f = 0.10000002 (2.4e-7 off) and
+// 1 - 0.999f = 0.00099998713 (1.3e-5 off): the moments then sit that far from Adam's, 4 and 200 float32 ulps, and the
+// parameters stay right only as long as the bias corrections carry the same error.
+struct AdamConsts {
+  float omb1, b2, omb2;        // 1 - beta1, beta2, 1 - beta2
+  float lb1, lb2;              // log(beta1), log(beta2)
+  float eps;
+  double b2d, omb2d;           // beta2, 1 - beta2 (the second moment is formed in double and rounded once)
+};
+static inline AdamConsts adam_consts(double beta1, double beta2, double eps) {
+  return AdamConsts{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)log(beta1), (float)log(beta2), (float)eps,
+                    beta2, 1.0 - beta2};
+}
+// 1 - beta^t = -expm1(t log beta): within 2 ulps for every t (powf of the rounded beta is off by t times beta's rounding,
+// and at t = 1 the difference from 1 magnifies it)
+__device__ __forceinline__ float adam_bias_corr(float log_beta, float t) { return -expm1f(__fmul_rn(t, log_beta)); }
+
 __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, float lr, float bc1, float bc2_sqrt,
-                                           float b1, float b2, float eps) {
-  m = __fmaf_rn(g - m, 1.0f - b1, m);
-  v = __fmaf_rn(__fmul_rn(g, g), 1.0f - b2, __fmul_rn(v, b2));
-  const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
+                                           const AdamConsts& k) {
+  m = __fmaf_rn(g - m, k.omb1, m);
+  // v in double, rounded once: g g is exact there, and the three float roundings of (g g)(1 - b2) + v b2 on top of
+  // float(0.001)'s own 4.7e-8 put the largest v, the square of the largest gradient, up to 1.8 ulp off
+  const double gd = (double)g;
+  v = __double2float_rn(__fma_rn(__dmul_rn(gd, gd), k.omb2d, __dmul_rn((double)v, k.b2d)));
+  const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), k.eps);
   return __fsub_rn(p, __fmul_rn(__fdiv_rn(lr, bc1), __fdiv_rn(m, denom)));
 }
 
@@ -60,12 +82,12 @@ struct TfAdam {
   float* step_count;
   unsigned int* block_counter;
   int offM, offb, offc;
-  float b1, b2, eps;
+  AdamConsts k;
 };
 
 __device__ __forceinline__ float tf_adam_elem(const TfAdam& ad, int i, float gi, float bc1, float bc2_sqrt) {
   float mi = ad.m[i], vi = ad.v[i];
-  const float pn = adam_elem(ad.p[i], gi, mi, vi, ad.lr_seg[ad.seg[i]], bc1, bc2_sqrt, ad.b1, ad.b2, ad.eps);
+  const float pn = adam_elem(ad.p[i], gi, mi, vi, ad.lr_seg[ad.seg[i]], bc1, bc2_sqrt, ad.k);
   ad.m[i] = mi;
   ad.v[i] = vi;
   ad.p[i] = pn;

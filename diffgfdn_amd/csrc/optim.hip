@@ -6,6 +6,8 @@
 // flat gradient buffer in place, and the update of every parameter of every group is a single
 // launch instead of ~100 tiny foreach kernels.  Maths = torch.optim.Adam (no amsgrad, no weight
 // decay):  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
+// beta1, beta2, eps arrive as the doubles the optimiser holds: 1 - beta and log(beta) are rounded to float once, from the
+// double (common.h adam_consts).
 #include "common.h"
 
 // step_count: device float holding t-1 on entry; every thread uses t = step_count + 1.
@@ -16,16 +18,16 @@ __global__ __launch_bounds__(1024) void k_adam(float* __restrict__ p, const floa
                                               float* __restrict__ m, float* __restrict__ v,
                                               const unsigned char* __restrict__ seg,
                                               const float* __restrict__ lr_seg,
-                                              float* __restrict__ step_count, int n, float b1,
-                                              float b2, float eps, int advance,
+                                              float* __restrict__ step_count, int n, AdamConsts k,
+                                              int advance,
                                               unsigned int* __restrict__ block_counter,
                                               float* __restrict__ mirror) {
   const float t = step_count[0] + 1.0f;
-  const float bc1 = 1.0f - powf(b1, t);
-  const float bc2_sqrt = sqrtf(1.0f - powf(b2, t));
+  const float bc1 = adam_bias_corr(k.lb1, t);
+  const float bc2_sqrt = sqrtf(adam_bias_corr(k.lb2, t));
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     float mi = m[i], vi = v[i];
-    p[i] = adam_elem(p[i], g[i], mi, vi, lr_seg[seg[i]], bc1, bc2_sqrt, b1, b2, eps);      // (lerp, as torch does)
+    p[i] = adam_elem(p[i], g[i], mi, vi, lr_seg[seg[i]], bc1, bc2_sqrt, k);      // (lerp, as torch does)
     m[i] = mi;
     v[i] = vi;
   }
@@ -54,13 +56,14 @@ __global__ void k_adam_advance(float* step_count) {
 }
 
 static int adam_step_run(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                         const float* lr_seg, float* step_count, int n, float beta1, float beta2,
-                         float eps, unsigned int* block_counter, void* stream, float* mirror = nullptr) {
+                         const float* lr_seg, float* step_count, int n, double beta1, double beta2,
+                         double eps, unsigned int* block_counter, void* stream, float* mirror = nullptr) {
   if (!p || !g || !m || !v || !seg || !lr_seg || !step_count || n <= 0) return GFDN_E_BADARG;
+  const AdamConsts k = adam_consts(beta1, beta2, eps);
   hipStream_t s = (hipStream_t)stream;
   if (n <= 16 * 1024) {          // one block: update + counter advance in a single launch
     hipLaunchKernelGGL(k_adam, dim3(1), dim3(1024), 0, s, p, g, m, v, seg, lr_seg, step_count, n,
-                       beta1, beta2, eps, 1, (unsigned int*)nullptr, mirror);
+                       k, 1, (unsigned int*)nullptr, mirror);
     GFDN_LAUNCH_CHECK();
     return 0;
   }
@@ -69,7 +72,7 @@ static int adam_step_run(float* p, const float* g, float* m, float* v, const uns
   int blocks = (n + 2047) / 2048;
   if (blocks > 512) blocks = 512;
   hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(256), 0, s, p, g, m, v, seg, lr_seg, step_count, n,
-                     beta1, beta2, eps, 0, block_counter, mirror);
+                     k, 0, block_counter, mirror);
   GFDN_LAUNCH_CHECK();
   if (!block_counter) {
     hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, s, step_count);
@@ -79,16 +82,16 @@ static int adam_step_run(float* p, const float* g, float* m, float* v, const uns
 }
 
 extern "C" int gfdn_adam_step(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                              const float* lr_seg, float* step_count, int n, float beta1, float beta2,
-                              float eps, void* stream) {
+                              const float* lr_seg, float* step_count, int n, double beta1, double beta2,
+                              double eps, void* stream) {
   return adam_step_run(p, g, m, v, seg, lr_seg, step_count, n, beta1, beta2, eps, nullptr, stream);
 }
 
 // block_counter: one zero-initialised uint32 owned by the optimiser (re-armed by every launch): the update and the
 // advance of step_count are then ONE launch whatever n is
 extern "C" int gfdn_adam_step_counted(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                                      const float* lr_seg, float* step_count, int n, float beta1, float beta2,
-                                      float eps, unsigned int* block_counter, void* stream) {
+                                      const float* lr_seg, float* step_count, int n, double beta1, double beta2,
+                                      double eps, unsigned int* block_counter, void* stream) {
   if (!block_counter) return GFDN_E_BADARG;
   return adam_step_run(p, g, m, v, seg, lr_seg, step_count, n, beta1, beta2, eps, block_counter, stream);
 }
@@ -97,8 +100,8 @@ extern "C" int gfdn_adam_step_counted(float* p, const float* g, float* m, float*
 // its buffer from two streams gives each range its own counter (a range reads and advances only its own: no ordering
 // between the two launches is needed) and keeps them equal through this entry point when it steps the whole buffer.
 extern "C" int gfdn_adam_step_mirrored(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                                       const float* lr_seg, float* step_count, float* mirror, int n, float beta1,
-                                       float beta2, float eps, unsigned int* block_counter, void* stream) {
+                                       const float* lr_seg, float* step_count, float* mirror, int n, double beta1,
+                                       double beta2, double eps, unsigned int* block_counter, void* stream) {
   if (!block_counter || !mirror) return GFDN_E_BADARG;
   return adam_step_run(p, g, m, v, seg, lr_seg, step_count, n, beta1, beta2, eps, block_counter, stream, mirror);
 }

@@ -362,7 +362,7 @@ int gfdn_tf_tail(const float* A0, const float* inv_gamma0, const float* grec0, i
                  const float* grec1, const float* b, const float* c, int nblk, int nper, const float* M, const float* gQ,
                  const float* Q, float* gb, float* gc, float* gM, float* flat_p, float* flat_m, float* flat_v,
                  const unsigned char* seg, const float* lr_seg, float* step_count, unsigned int* block_counter, int offM,
-                 int offb, int offc, float beta1, float beta2, float eps, float* Q_next, float* QQ_next, float* coef_next,
+                 int offb, int offc, double beta1, double beta2, double eps, float* Q_next, float* QQ_next, float* coef_next,
                  float* coef_sub_next, void* stream);
 /* out[r] = sum_p part[r * cols + p]: one wavefront per row, fixed order */
 int gfdn_tf_rows_sum(const float* part, int cols, int rows, float* out, void* stream);
@@ -467,7 +467,7 @@ int gfdn_tf8_tail(const float* A0, const float* inv_gamma0, const float* part0, 
                   int nparts1, const float* b, const float* c, int nblk, int nper, const float* M, const float* gQ,
                   const float* Q, float* gb, float* gc, float* gM, void* work, float* flat_p, float* flat_m, float* flat_v,
                   const unsigned char* seg, const float* lr_seg, float* step_count, unsigned int* block_counter, int offM,
-                  int offb, int offc, float beta1, float beta2, float eps, float* Q_next, float* QQ_next, float* c_next,
+                  int offb, int offc, double beta1, double beta2, double eps, float* Q_next, float* QQ_next, float* c_next,
                   void* stream);
 /* ---- polynomial passes of the same blocks on the reference's own grid by fast transforms (csrc/polyfft.hip).
  * Preconditions: INTEGER delay lengths (config.py:131-140) and the grid z_k = e^{2 pi i k / nfft}, k = 0 .. nfft / 2
@@ -1014,20 +1014,21 @@ int gfdn_pick_rows(const long long* table, long long* state, long long* idx, int
  * All parameters are views into one flat fp32 buffer p (n floats), gradients into g, Adam moments
  * into m, v.  seg[i] (uint8) = learning-rate group of element i, lr_seg[group] the group's lr (device,
  * so that StepLR edits it without re-recording a HIP graph), step_count (device float) the number of
- * updates done so far -- advanced by one by this call.                                          */
+ * updates done so far -- advanced by one by this call.  beta1, beta2, eps: the doubles the optimiser
+ * holds (1 - beta and the bias corrections are formed from them, not from their float roundings).   */
 int gfdn_adam_step(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                   const float* lr_seg, float* step_count, int n, float beta1, float beta2,
-                   float eps, void* stream);
+                   const float* lr_seg, float* step_count, int n, double beta1, double beta2,
+                   double eps, void* stream);
 /* the same in ONE launch for any n: block_counter = a zero-initialised uint32 of the caller's (the last workgroup to
  * finish advances step_count and re-arms it)                                                              */
 int gfdn_adam_step_counted(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                           const float* lr_seg, float* step_count, int n, float beta1, float beta2,
-                           float eps, unsigned int* block_counter, void* stream);
+                           const float* lr_seg, float* step_count, int n, double beta1, double beta2,
+                           double eps, unsigned int* block_counter, void* stream);
 /* the same, also writing the advanced count to `mirror` (a second counter of the caller's that must stay equal to
  * step_count: an optimiser that steps two ranges of its buffer from two streams keeps one counter per range)  */
 int gfdn_adam_step_mirrored(float* p, const float* g, float* m, float* v, const unsigned char* seg,
-                            const float* lr_seg, float* step_count, float* mirror, int n, float beta1, float beta2,
-                            float eps, unsigned int* block_counter, void* stream);
+                            const float* lr_seg, float* step_count, float* mirror, int n, double beta1, double beta2,
+                            double eps, unsigned int* block_counter, void* stream);
 
 /* ---- full-band render of a band bank  (run_subband_training_treble.py:207-375 ``inferencing``: get_response, fftconvolve with
  * the band's reconstructing FIR :321-324, sum over the bands per receiver :358) as one skinny product (csrc/render.hip):

@@ -232,6 +232,7 @@ SIGNATURES = {
     "gfdn_moving_compose": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, c_int,
                                     _P]),
     "gfdn_moving_ola": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "gfdn_dir_render": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
 }
 
 _lib = None

@@ -214,6 +214,14 @@ class DirectionalBank:
     def _lane(self, q: int):
         return self.lanes[q % len(self.lanes)]
 
+    def render(self, z_values, norm_listener_position, taps, length: int, directional: bool = True, rows=None, out=None,
+               chunk: int = 4096):
+        """The spatial RIRs of all receivers from the bank's bands as they stand (``subband.infer_directional_bands`` on
+        the trainers' nets, band q filtered with ``taps[q]``): (len(rows) or R, J or (order+1)^2, length) float32."""
+        from .subband import infer_directional_bands
+        return infer_directional_bands([st.tr.net for st in self.steps], z_values, norm_listener_position, taps, length,
+                                       directional=directional, rows=rows, out=out, chunk=chunk)
+
     def capture(self):
         with contextlib.ExitStack() as scopes:
             for st in self.steps:

@@ -1974,6 +1974,60 @@ def render_mix(d, w, c, rows=None, out=None) -> torch.Tensor:
     return out
 
 
+DIR_RENDER_MAX_S, DIR_RENDER_MAX_LS, DIR_RENDER_MAX_J = 32, 16, 32
+
+
+def _overlap(x: torch.Tensor, y: torch.Tensor) -> bool:
+    """do the address ranges of two strided tensors of one storage meet?"""
+    if x.untyped_storage().data_ptr() != y.untyped_storage().data_ptr() or x.numel() == 0 or y.numel() == 0:
+        return False
+
+    def span(t):
+        lo = t.data_ptr()
+        return lo, lo + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+    (x0, x1), (y0, y1) = span(x), span(y)
+    return x0 < y1 and y0 < x1
+
+
+def dir_render(w, c, Ls: int, a=None, out=None) -> torch.Tensor:
+    """out (R, J, n) = a @ ambi (directional RIRs) or, without ``a``, out (R, Ls, n) = ambi (ambisonic RIRs), with
+    ambi[i][l] = sum_s w[i][s][l] c[s Ls + l]: the spatial render of the directional bands (csrc/dirrender.hip).  w (R, S, Ls)
+    or (R, S Ls) the receivers' SH weights, c (S Ls, n) the filtered signals (channel the faster index; may be a row-strided
+    view), a (J, Ls) the analysis matrix.  ``out``: a float32 (R, J or Ls, n) view with contiguous samples and one row pitch
+    to fill; it must not overlap c.  S <= 32, Ls <= 16, J <= 32: beyond, this raises (``subband.directional_mix`` is the
+    caller that falls back)."""
+    _need_gpu(w, c, a, out)
+    Ls = int(Ls)
+    w = _f(w)
+    if Ls < 1 or c.dim() != 2 or w.dim() not in (2, 3) or w.numel() == 0 or c.shape[1] == 0 or c.shape[0] % Ls:
+        raise RuntimeError("dir_render: w (R, S, Ls) and c (S Ls, n) expected")
+    R, n = w.shape[0], c.shape[1]
+    S = c.shape[0] // Ls
+    if w.numel() != R * S * Ls or (w.dim() == 3 and w.shape[2] != Ls):
+        raise RuntimeError("dir_render: w (R, S, Ls) and c (S Ls, n) expected")
+    if c.dtype != _f32 or c.stride(1) != 1 or c.stride(0) < n or c.stride(0) >= 2 ** 31:
+        raise RuntimeError(f"dir_render: c must be a float32 matrix with contiguous rows of at least {n} samples")
+    c = c.detach()
+    J = 0
+    if a is not None:
+        a = _f(a)
+        if a.dim() != 2 or a.shape[1] != Ls or a.shape[0] == 0:
+            raise RuntimeError("dir_render: a (J, Ls) expected")
+        J = a.shape[0]
+    nrow = J if a is not None else Ls
+    if out is None:
+        out = torch.empty((R, nrow, (n + 3) // 4 * 4), dtype=_f32, device=c.device)[:, :, :n]
+    else:
+        if tuple(out.shape) != (R, nrow, n):
+            raise RuntimeError(f"dir_render: out must be ({R}, {nrow}, {n})")
+        out = _band_signals(out, "out", n, "dir_render")
+        if _overlap(out, c):
+            raise RuntimeError("dir_render: out must not overlap c")
+    _lib.check(_lib.load().gfdn_dir_render(_p(w), _p(c), c.stride(0), _p(a), R, S, Ls, J, n, _p(out), out.stride(1),
+                                           _stream()), "gfdn_dir_render")
+    return out
+
+
 def _band_signals(t, name: str, L: int, what: str) -> torch.Tensor:
     """a (rows, bands, >= L) float32 tensor with contiguous samples and ONE pitch: stride(0) = bands * stride(1)"""
     if (t.dtype != _f32 or t.dim() != 3 or t.numel() == 0 or t.shape[2] < L or t.stride(2) != 1 or t.stride(1) < L

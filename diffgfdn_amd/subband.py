@@ -108,6 +108,130 @@ def infer_bank(bank, dataset, taps, rows=None, out: Optional[torch.Tensor] = Non
     return ops.render_mix(D, W, C, rows=sel, out=out)
 
 
+def same_convolve(h: torch.Tensor, taps: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.signal.fftconvolve(h[r], taps, mode='same') for every row r: the L = len(h[r]) samples of the full convolution
+    from sample (M - 1) // 2 on (scipy centres the result on its first argument)."""
+    L, M = h.shape[-1], taps.numel()
+    y = full_convolve(h, taps)[..., (M - 1) // 2:(M - 1) // 2 + L]
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
+def directional_mix_torch(W: torch.Tensor, C: torch.Tensor, Ls: int, A: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hip_ops.dir_render`` in stock tensor operations, the two-stage formulation: Ls skinny products into the ambisonic
+    RIRs of all receivers, then the J x Ls contraction.  For the shapes the kernel does not take (and as its yardstick in
+    tools/time_directional_render.py)."""
+    R, n = W.shape[0], C.shape[1]
+    W3, C3 = W.reshape(R, -1, Ls), C.reshape(-1, Ls, C.shape[1])
+    ambi = out if (A is None and out is not None) else torch.empty((R, Ls, n), dtype=torch.float32, device=C.device)
+    for l in range(Ls):
+        ambi[:, l] = W3[:, :, l] @ C3[:, l]
+    if A is None:
+        return ambi
+    res = torch.matmul(A, ambi)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def directional_mix(W: torch.Tensor, C: torch.Tensor, Ls: int, A: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(R, J or Ls, n): the receivers' directional (``A`` (J, Ls) given) or ambisonic RIRs from their SH weights W (R, S, Ls)
+    and the filtered signals C (S Ls, n): ``hip_ops.dir_render`` (csrc/dirrender.hip) within its limits (S <= 32, Ls <= 16,
+    J <= 32), the same result from ``directional_mix_torch`` beyond them."""
+    S = C.shape[0] // Ls
+    if (S > ops.DIR_RENDER_MAX_S or Ls > ops.DIR_RENDER_MAX_LS
+            or (A is not None and A.shape[0] > ops.DIR_RENDER_MAX_J)):
+        return directional_mix_torch(W, C, Ls, A, out)
+    return ops.dir_render(W, C, Ls, a=A, out=out)
+
+
+def directional_band_signals(nets, z_values: torch.Tensor, taps: torch.Tensor, length: int) -> torch.Tensor:
+    """C (Q G Ls, length): per band q and delay line n = g Ls + l the line's response with its output gain, c_n Y_q[:, n],
+    brought to the time domain (irfft, n = 2 (K - 1)), cut to ``length`` and through the band's reconstructing FIR
+    (``same_convolve``) -- Q G Ls signals whatever the number of receivers.  The cut comes before the filter, as in the
+    reference (inference.py:479-481, then :807-810).  The rows' pitch is a multiple of four samples."""
+    K = z_values.shape[-1]
+    nfft = 2 * (K - 1)
+    if nfft < 16 or nfft & (nfft - 1):
+        raise ValueError("directional_band_signals: the frequency grid of a power-of-two transform (K = nfft / 2 + 1)")
+    N = nets[0].num_groups * nets[0].num_delay_lines_per_group
+    C = torch.empty((len(nets) * N, (length + 3) // 4 * 4), dtype=torch.float32, device=z_values.device)[:, :length]
+    for q, net in enumerate(nets):
+        net.feedback_loop.new_forward()
+        Y = net.delay_line_responses(z_values, transpose=True)                     # (K, N)
+        X = (Y * net.output_gains.reshape(1, -1)).transpose(0, 1).contiguous()     # (N, K)
+        h = ops.irfft_pow2_fwd(X, nfft)[:, :length]
+        same_convolve(h.contiguous(), taps[q], out=C[q * N:(q + 1) * N])
+    return C
+
+
+@torch.no_grad()
+def infer_directional_bands(nets, z_values, norm_listener_position, taps, length: int, directional: bool = True, rows=None,
+                            out: Optional[torch.Tensor] = None, chunk: int = 4096) -> torch.Tensor:
+    """The spatial RIRs of all receivers from the trained directional bands in one pass: what the reference's
+    ``infer_all_octave_bands_directional_fdn`` (inference.py:676-881, with ``InferDiffDirectionalFDN.get_model_output``
+    :402-481) builds band by band and receiver by receiver -- get_response (h = irfft(H_sh), n = 2 (K - 1)), the cut to
+    ``edc_len_samps``, optionally the conversion to directional RIRs with the analysis matrix (:387-400),
+    fftconvolve(.., mode='same') with the band's reconstructing FIR (:807-810), the sum over the bands per receiver
+    (:837-862).  Neither the inverse transform, the cut nor the FIR depends on the receiver, which enters only through its
+    G x (order+1)^2 SH weights per band (``sh_output_scalars`` with normalised weights):
+
+        C[q][g][l]    = same_conv(irfft(c_{g,l} Y_q[:, g Ls + l], n = 2 (K - 1))[:length], taps_q)     Q G Ls signals
+        ambi[r][l][t] = sum_{q,g} w_q[r][g][l] C[q][g][l][t]                                        (directional=False)
+        dir[r][j][t]  = sum_l A[j][l] ambi[r][l][t]                                                 (directional=True)
+
+    (conversion and band sum are linear: converting after the sum is the reference's convert-then-sum up to rounding).
+    All receivers are ONE launch of ``hip_ops.dir_render`` (csrc/dirrender.hip), the ambisonic RIRs never stored in the
+    directional mode; beyond the kernel's limits (Q G > 32, more than 16 channels or 32 directions) the same result comes
+    from stock tensor operations (``directional_mix_torch``).
+
+    ``nets``: the Q trained DiffDirectionalFDNVarReceiverPos models, one per band, with the same G, order and analysis
+    matrix; ``z_values`` (K,) the frequency grid, K = 2^p + 1; ``norm_listener_position`` (R, 3) the receivers' normalised
+    positions; ``taps`` (Q, M) the bands' reconstructing FIRs; ``length``: the reference's ``edc_len_samps``, clamped to
+    2 (K - 1); ``directional=False`` is the reference's ``sum_ambi_directly=True``; ``rows``: receivers to render, in this
+    order (default: all R); ``out``: a (len(rows) or R, J or Ls, length) float32 view to fill; ``chunk``: positions per
+    evaluation of a band's weight network.  Returns (len(rows) or R, J or (order+1)^2, length) float32.
+
+    Not covered: ``apply_filter_norm`` (the reference's driver passes False), the conversion of the summed directional RIRs
+    back to ambisonics (:864-881, spaudiopy), the checkpoints and per-band pickles the reference reads and writes on the
+    way, and binaural rendering (sound_examples.py:356-535), which consumes this function's result."""
+    nets = list(nets)
+    if not nets:
+        raise ValueError("infer_directional_bands: no bands")
+    dev = nets[0].output_gains.device
+    G, Ls = nets[0].num_groups, nets[0].num_delay_lines_per_group
+    A = nets[0].sh_output_scalars.analysis_matrix
+    for net in nets[1:]:
+        An = net.sh_output_scalars.analysis_matrix
+        if (net.num_groups != G or net.num_delay_lines_per_group != Ls or An.shape != A.shape
+                or not torch.equal(An.to(A.device), A)):
+            raise ValueError("infer_directional_bands: the bands must share groups, order and analysis matrix")
+    if not torch.is_tensor(taps):
+        taps = torch.stack([torch.as_tensor(t) for t in taps])
+    taps = taps.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if taps.dim() != 2 or taps.shape[0] != len(nets) or taps.shape[1] < 1:
+        raise ValueError("infer_directional_bands: one row of taps per band")
+    pos = norm_listener_position.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
+    if rows is not None:
+        sel = _edc_rows(rows, pos.shape[0], dev, "infer_directional_bands")
+        pos = pos[sel]
+    z = z_values.to(dev)
+    L = max(1, min(int(length), 2 * (z.shape[-1] - 1)))
+    C = directional_band_signals(nets, z, taps, L)
+    R = pos.shape[0]
+    W = torch.empty((R, len(nets), G, Ls), dtype=torch.float32, device=dev)
+    for q, net in enumerate(nets):
+        for r0 in range(0, R, int(chunk)):
+            W[r0:r0 + chunk, q] = net.sh_output_scalars({'norm_listener_position': pos[r0:r0 + chunk]},
+                                                        normalise_weights=True)
+    return directional_mix(W.view(R, len(nets) * G, Ls), C, Ls, A.to(dev) if directional else None, out)
+
+
 def band_split(x: torch.Tensor, analysis_taps: torch.Tensor, length: int, chunk: int = 32,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(rows, A, length) float32: the first ``length`` samples of ``full_convolve(x[r], analysis_taps[k])`` for every row

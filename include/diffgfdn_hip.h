@@ -1105,6 +1105,21 @@ int gfdn_moving_compose(const float* dh_c64, int ld_d, const long long* rows, co
 int gfdn_moving_ola(const float* s, int ld_s, int nseg, int k0, int P, int h, int Lr, int Fd, const float* tail_in,
                     float* tail_out, float* out, void* stream);
 
+/* ---- spatial render of the directional bands  (inference.py:676-881 ``infer_all_octave_bands_directional_fdn``: per band and
+ * receiver get_response, the cut to edc_len_samps, the optional conversion with the analysis matrix :387-400,
+ * fftconvolve(.., 'same') with the band's reconstructing FIR :807-810, the sum over the bands :837-862) for all receivers in
+ * one launch (csrc/dirrender.hip).  The receiver enters only through its SH weights:
+ *     ambi[i][l][t] = sum_{s < S} w[(i S + s) Ls + l] c[(s Ls + l) ld_c + t]                    i < R, l < Ls, t < n, float32
+ *     a != NULL:  out[(i J + j) ld_out + t]  = sum_{l < Ls} a[j Ls + l] ambi[i][l][t]           j < J   (directional RIRs)
+ *     a == NULL:  out[(i Ls + l) ld_out + t] = ambi[i][l][t]                                    (ambisonic RIRs; J is ignored)
+ * c (S Ls, ld_c): the filtered signals, signal s = band G + g, channel l the faster index; w (R, S, Ls) the receivers'
+ * weights; a (J, Ls) the analysis matrix.  acc = 0, acc = fma(w, c, acc) for s = 0 .. S-1; d = 0, d = fma(a, acc, d) for
+ * l = 0 .. Ls-1: a receiver's bits do not depend on the other receivers of the launch.  The ambisonic values stay in
+ * registers in the directional mode.  S <= 32, Ls <= 16, J <= 32 (GFDN_E_UNSUPPORTED above).  4-byte accesses: no alignment
+ * requirement beyond float; pitches >= n; out must not overlap w, c or a; nothing is written behind sample n - 1 of a row. */
+int gfdn_dir_render(const float* w, const float* c, int ld_c, const float* a, int R, int S, int Ls, int J, int n, float* out,
+                    int ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

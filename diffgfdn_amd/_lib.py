@@ -233,6 +233,9 @@ SIGNATURES = {
                                     _P]),
     "gfdn_moving_ola": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "gfdn_dir_render": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "gfdn_binaural_compose": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_float, _P, c_int, _P]),
+    "gfdn_binaural_ola": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

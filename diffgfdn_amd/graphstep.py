@@ -222,6 +222,17 @@ class DirectionalBank:
         return infer_directional_bands([st.tr.net for st in self.steps], z_values, norm_listener_position, taps, length,
                                        directional=directional, rows=rows, out=out, chunk=chunk)
 
+    def render_binaural(self, z_values, norm_listener_position, taps, length: int, hrir_sh, path, rotations, stimulus,
+                        update_ms: float = 100.0, alpha: float = 0.5, fade_len_ms: Optional[float] = None,
+                        sample_rate: Optional[float] = None, chunk: int = 32, out=None):
+        """A dry stimulus heard binaurally by a listener who moves along ``path`` and turns their head, from the bank's
+        bands as they stand (``subband.render_binaural_moving_listener_bands`` on the trainers' nets): (P h, 2) float32."""
+        from .subband import render_binaural_moving_listener_bands
+        return render_binaural_moving_listener_bands([st.tr.net for st in self.steps], z_values, norm_listener_position, taps,
+                                                     length, hrir_sh, path, rotations, stimulus, update_ms=update_ms,
+                                                     alpha=alpha, fade_len_ms=fade_len_ms, sample_rate=sample_rate,
+                                                     chunk=chunk, out=out)
+
     def capture(self):
         with contextlib.ExitStack() as scopes:
             for st in self.steps:

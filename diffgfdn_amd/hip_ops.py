@@ -2329,6 +2329,121 @@ def moving_ola(s, k0: int, P: int, h: int, Lr: int, Fd: int, out, tail_in, tail_
     return out
 
 
+BINAURAL_MAX_S, BINAURAL_MAX_LS = 32, 16
+
+
+def _spectra3(t, name: str, rows: int, F: int, what: str) -> torch.Tensor:
+    """a complex64 (.., rows, F) tensor with contiguous bins and ONE row pitch: stride(0) = rows * stride(1)"""
+    if (t.dtype != _c64 or t.dim() != 3 or t.numel() == 0 or t.shape[1] != rows or t.shape[2] != F or t.stride(2) != 1
+            or t.stride(1) < F or (t.shape[0] > 1 and t.stride(0) != rows * t.stride(1)) or t.stride(1) >= 2 ** 30):
+        raise RuntimeError(f"{what}: {name} must be a complex64 (.., {rows}, {F}) tensor with contiguous bins and one row "
+                           "pitch")
+    return t.detach()
+
+
+def binaural_compose(rot, Hh, alpha: float, k0: int, nseg: int, W=None, Ch=None, Ah=None, path=None, row_off: int = 0,
+                     out=None, *, rows_checked: bool = False) -> torch.Tensor:
+    """B (nseg, 2, Kb) complex64: the binaural room transfer functions of the segments k0 .. k0 + nseg - 1 of a path
+    (reference sound_examples.py:425-472 ``get_binaural_rir``; csrc/binaural.hip):
+
+        B_k[e] = sum_n conj(Hh[n][e]) sum_m Rw_k[n][m] Aw_k[m],   Rw_k = alpha rot[k] + (1 - alpha) rot[k - 1],
+        Aw_k = alpha A_k + (1 - alpha) A_{k-1}    (k = 0: the raw values; NO recursion: the raw previous position)
+
+    with A_k[m] = sum_s W[row_k][s][m] Ch[s Ls + m] (bank mode: W (rows, S, Ls) SH weights, Ch (S Ls, Kb) spectra of the
+    directional band signals) or A_k = Ah[row_k] (rows mode: Ah (rows, Ls, Kb) a store of ambisonic spectra);
+    row_k = (path[k] if given else k) - row_off.  ``rot`` (P, Ls, Ls) float32 and ``path`` (P,) int64 are WHOLE-PATH arrays:
+    segment k0 - 1 is read, no state is kept, chunks give the bits of one launch.  Hh (Ls, 2, Kb) complex64.  S <= 32,
+    Ls <= 16.  ``out``: a complex64 (nseg, 2, Kb) view with one row pitch to fill.  ``path`` is range-checked here (one host
+    sync) unless ``rows_checked``."""
+    what = "binaural_compose"
+    _need_gpu(rot, Hh, W, Ch, Ah, path, out)
+    k0, nseg, row_off = int(k0), int(nseg), int(row_off)
+    if rot.dim() != 3 or rot.shape[1] != rot.shape[2] or rot.numel() == 0 or Hh.dim() != 3:
+        raise RuntimeError(f"{what}: rot (P, Ls, Ls) and Hh (Ls, 2, Kb) expected")
+    rot = _f(rot)
+    P, Ls = rot.shape[0], rot.shape[1]
+    Kb = Hh.shape[2]
+    Hh = _spectra3(Hh, "Hh", 2, Kb, what)
+    if Hh.shape[0] != Ls:
+        raise RuntimeError(f"{what}: rot (P, Ls, Ls) and Hh (Ls, 2, Kb) expected")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise RuntimeError(f"{what}: 0 <= alpha <= 1")
+    if k0 < 0 or nseg < 1 or k0 + nseg > P or row_off < 0:
+        raise RuntimeError(f"{what}: segments k0 .. k0 + nseg - 1 of a path of P")
+    if (W is None) != (Ch is None) or (W is None) == (Ah is None):
+        raise RuntimeError(f"{what}: either W and Ch (bank mode) or Ah (rows mode)")
+    S = 0
+    if W is not None:
+        W = _f(W)
+        if W.dim() != 3 or W.shape[2] != Ls or W.numel() == 0:
+            raise RuntimeError(f"{what}: W (rows, S, Ls) expected")
+        nrows, S = W.shape[0], W.shape[1]
+        Ch = _spectra_rows(Ch, "Ch", Kb, what)
+        if Ch.shape[0] != S * Ls:
+            raise RuntimeError(f"{what}: Ch (S Ls, Kb) expected")
+    else:
+        Ah = _spectra3(Ah, "Ah", Ls, Kb, what)
+        nrows = Ah.shape[0]
+    if S > BINAURAL_MAX_S or Ls > BINAURAL_MAX_LS:
+        raise RuntimeError(f"{what}: at most {BINAURAL_MAX_S} band signals per channel and {BINAURAL_MAX_LS} channels")
+    lo = max(k0 - 1, 0)
+    if path is not None:
+        if path.dtype != torch.long or path.dim() != 1 or path.shape[0] != P or not path.is_contiguous():
+            raise RuntimeError(f"{what}: path must be a contiguous int64 ({P},) vector")
+        if not rows_checked:
+            used = path[lo:k0 + nseg]
+            if int(used.min()) - row_off < 0 or int(used.max()) - row_off >= nrows:
+                raise RuntimeError(f"{what}: path outside the rows")
+    elif lo - row_off < 0 or k0 + nseg - 1 - row_off >= nrows:
+        raise RuntimeError(f"{what}: one row per segment from k0 - 1 on (or pass path)")
+    if out is None:
+        out = torch.empty((nseg, 2, Kb), dtype=_c64, device=rot.device)
+    else:
+        if out.dim() != 3 or out.shape[0] != nseg:
+            raise RuntimeError(f"{what}: out must be (nseg, 2, Kb)")
+        out = _spectra3(out, "out", 2, Kb, what)
+    ld = lambda t: max(t.stride(-2), t.shape[-1])           # noqa: E731  (a single row's stride says nothing)
+    _lib.check(_lib.load().gfdn_binaural_compose(_p(W), _p(Ch), 0 if Ch is None else _pitch(Ch), S, _p(Ah),
+                                                 0 if Ah is None else ld(Ah), _p(path), row_off, nrows, _p(rot), _p(Hh),
+                                                 ld(Hh), P, k0, nseg, Kb, Ls, float(alpha), _p(out), ld(out), _stream()),
+               "gfdn_binaural_compose")
+    return out
+
+
+def binaural_ola(s, k0: int, P: int, h: int, nb: int, Fd: int, out, tail_in, tail_out) -> torch.Tensor:
+    """Overlap-add the two-ear time-domain segments ``s`` (nseg, 2, >= h + nb - 1) of a chunk -- segments k0 .. k0 + nseg - 1
+    of a path of P -- into ``out`` (P h, 2) float32 with the reference's square-root cross-fade (sound_examples.py:474-535;
+    csrc/binaural.hip): segment k covers out[k h : k h + min(h + nb - 1, P h - k h)]; for k >= 1 its first Fd samples enter
+    as t_{k-1} fade_out + s_k fade_in, fade_in = sqrt(0.5 (1 + linspace(-1, 1, Fd))), fade_out = sqrt(0.5 (1 - ..)),
+    t_{k-1} the last Fd samples of the cut segment before (``tail_in`` (Fd, 2) for the chunk's first segment, k0 > 0).
+    ``tail_out`` (Fd, 2), another buffer, receives this chunk's tail.  ``out`` is zeroed by the caller before the first
+    chunk.  Gather form: chunks give the same bits.  1 <= Fd <= h."""
+    what = "binaural_ola"
+    _need_gpu(s, out, tail_in, tail_out)
+    k0, P, h, nb, Fd = int(k0), int(P), int(h), int(nb), int(Fd)
+    if h < 1 or P < 1 or nb < 1 or not 1 <= Fd <= h:
+        raise RuntimeError(f"{what}: h >= 1, P >= 1, nb >= 1 and 1 <= Fd <= h")
+    lfull = h + nb - 1
+    if (s.dtype != _f32 or s.dim() != 3 or s.numel() == 0 or s.shape[1] != 2 or s.shape[2] < lfull or s.stride(2) != 1
+            or s.stride(1) < lfull or (s.shape[0] > 1 and s.stride(0) != 2 * s.stride(1)) or s.stride(1) >= 2 ** 31):
+        raise RuntimeError(f"{what}: s must be a float32 (nseg, 2, >= {lfull}) tensor with contiguous samples and one row "
+                           "pitch")
+    s = s.detach()
+    nseg = s.shape[0]
+    if k0 < 0 or k0 + nseg > P or P * h >= 2 ** 31:
+        raise RuntimeError(f"{what}: segments k0 .. k0 + nseg - 1 of a path of P, with P h < 2^31")
+    if out.dtype != _f32 or tuple(out.shape) != (P * h, 2) or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be a contiguous float32 ({P * h}, 2) matrix")
+    for t, name in ((tail_in, "tail_in"), (tail_out, "tail_out")):
+        if t is not None and (t.dtype != _f32 or tuple(t.shape) != (Fd, 2) or not t.is_contiguous()):
+            raise RuntimeError(f"{what}: {name} must be a contiguous float32 ({Fd}, 2) matrix")
+    if tail_out is None or (k0 > 0 and tail_in is None) or (tail_in is not None and tail_in.data_ptr() == tail_out.data_ptr()):
+        raise RuntimeError(f"{what}: tail_out, and tail_in behind the path's first chunk, as two buffers")
+    _lib.check(_lib.load().gfdn_binaural_ola(_p(s), s.stride(1), nseg, k0, P, h, nb, Fd, _p(tail_in), _p(tail_out), _p(out),
+                                             _stream()), "gfdn_binaural_ola")
+    return out
+
+
 def rfft_pow2_f64(x, n: int, kout: Optional[int] = None) -> torch.Tensor:
     """x (batch, T <= n) float64 -> the first ``kout`` (default n / 2 + 1) bins of rfft(x, n) as complex128 (csrc/fft64.hip:
     float64 radix-2 passes -- dataset constants only, speed is not the point)."""

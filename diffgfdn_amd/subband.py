@@ -199,10 +199,19 @@ def infer_directional_bands(nets, z_values, norm_listener_position, taps, length
 
     Not covered: ``apply_filter_norm`` (the reference's driver passes False), the conversion of the summed directional RIRs
     back to ambisonics (:864-881, spaudiopy), the checkpoints and per-band pickles the reference reads and writes on the
-    way, and binaural rendering (sound_examples.py:356-535), which consumes this function's result."""
+    way.  Binaural rendering (sound_examples.py:356-535), which consumes this function's result, is
+    ``render_binaural_moving_listener_bands`` (from the bands, in one pass) and ``render_binaural_moving_listener``."""
+    W, C, Ls, A = _directional_inputs(nets, z_values, norm_listener_position, taps, length, rows, chunk,
+                                      "infer_directional_bands")
+    return directional_mix(W, C, Ls, A if directional else None, out)
+
+
+def _directional_inputs(nets, z_values, norm_listener_position, taps, length: int, rows, chunk: int, what: str):
+    """the band checks of ``infer_directional_bands`` and what its mix takes: (W (R, Q G, Ls) the receivers' normalised SH
+    weights, C (Q G Ls, L) the filtered band signals, Ls, the analysis matrix)"""
     nets = list(nets)
     if not nets:
-        raise ValueError("infer_directional_bands: no bands")
+        raise ValueError(f"{what}: no bands")
     dev = nets[0].output_gains.device
     G, Ls = nets[0].num_groups, nets[0].num_delay_lines_per_group
     A = nets[0].sh_output_scalars.analysis_matrix
@@ -210,15 +219,15 @@ def infer_directional_bands(nets, z_values, norm_listener_position, taps, length
         An = net.sh_output_scalars.analysis_matrix
         if (net.num_groups != G or net.num_delay_lines_per_group != Ls or An.shape != A.shape
                 or not torch.equal(An.to(A.device), A)):
-            raise ValueError("infer_directional_bands: the bands must share groups, order and analysis matrix")
+            raise ValueError(f"{what}: the bands must share groups, order and analysis matrix")
     if not torch.is_tensor(taps):
         taps = torch.stack([torch.as_tensor(t) for t in taps])
     taps = taps.detach().to(device=dev, dtype=torch.float32).contiguous()
     if taps.dim() != 2 or taps.shape[0] != len(nets) or taps.shape[1] < 1:
-        raise ValueError("infer_directional_bands: one row of taps per band")
+        raise ValueError(f"{what}: one row of taps per band")
     pos = norm_listener_position.detach().to(device=dev, dtype=torch.float32).reshape(-1, 3)
     if rows is not None:
-        sel = _edc_rows(rows, pos.shape[0], dev, "infer_directional_bands")
+        sel = _edc_rows(rows, pos.shape[0], dev, what)
         pos = pos[sel]
     z = z_values.to(dev)
     L = max(1, min(int(length), 2 * (z.shape[-1] - 1)))
@@ -229,7 +238,7 @@ def infer_directional_bands(nets, z_values, norm_listener_position, taps, length
         for r0 in range(0, R, int(chunk)):
             W[r0:r0 + chunk, q] = net.sh_output_scalars({'norm_listener_position': pos[r0:r0 + chunk]},
                                                         normalise_weights=True)
-    return directional_mix(W.view(R, len(nets) * G, Ls), C, Ls, A.to(dev) if directional else None, out)
+    return W.view(R, len(nets) * G, Ls), C, Ls, A.to(dev)
 
 
 def band_split(x: torch.Tensor, analysis_taps: torch.Tensor, length: int, chunk: int = 32,
@@ -562,8 +571,9 @@ def render_moving_listener_bank(bank, dataset, taps, path, stimulus, update_ms: 
     to the bank's; ``out``: a contiguous float32 (P h,) buffer to fill.  Scope: P >= 1, h >= 1 and 1 <= Fd <= h (at Fd = 0
     the reference raises, above h its tail buffer keeps stale samples: ValueError here), 0 <= alpha <= 1.  Every call
     starts fresh: the ``prev_filter`` that the reference leaves on its object between calls is not reproduced.  Not covered:
-    the late-RIR variant (pass late RIRs to ``render_moving_listener``), binaural / HRTF rendering, loudness
-    normalisation, the animation, wav export.
+    the late-RIR variant (pass late RIRs to ``render_moving_listener``), loudness normalisation, the animation, wav
+    export.  Binaural / HRTF rendering of the directional model is ``render_binaural_moving_listener_bands`` and
+    ``render_binaural_moving_listener``.
     Returns (P h,) float32 on the bank's device."""
     what = "render_moving_listener_bank"
     dev = bank.input_gains.device
@@ -618,6 +628,176 @@ def render_moving_listener(rirs, path, stimulus, fs: float, update_ms: float = 1
         r = rirs[sel[k0:k1]].to(device=dev, dtype=torch.float32)
         return ops.rfft_pow2(r, n), None, None, None
     return _moving_run(x, P, h, Fd, Lr, n, float(alpha), int(chunk), out, chunk_inputs)
+
+
+def _binaural_plan(P: int, L: int, fs: float, update_ms: float, alpha: float, fade_len_ms, rotations, hrir_sh, Ls: int,
+                   dev, what: str):
+    """(h, Fd, nb, n2, rot (P, Ls, Ls), Hh (Ls, 2, nb / 2 + 1)) of the reference's binaural render; ValueError outside the
+    declared scope"""
+    fade_len_ms = update_ms if fade_len_ms is None else fade_len_ms         # sound_examples.py:478
+    if L < 9:
+        raise ValueError(f"{what}: ambisonic RIRs of at least 9 samples (the transforms start at 16 points)")
+    nb = 1 << (L - 1).bit_length()                                          # :408, 2^ceil(log2 L)
+    h, Fd, n2 = _moving_plan(P, nb, fs, update_ms, alpha, fade_len_ms, what)
+    rot = torch.as_tensor(rotations).detach().to(device=dev, dtype=torch.float32)
+    if tuple(rot.shape) != (P, Ls, Ls):
+        raise ValueError(f"{what}: rotations must be ({P}, {Ls}, {Ls}): one real SH rotation matrix per path position")
+    hr = torch.as_tensor(hrir_sh).detach().to(device=dev, dtype=torch.float32)
+    if hr.dim() != 3 or hr.shape[0] != Ls or hr.shape[1] != 2 or hr.shape[2] < 1:
+        raise ValueError(f"{what}: hrir_sh must be ({Ls}, 2, Mh): the SH-domain HRIRs of both ears")
+    if hr.shape[2] > nb:
+        raise ValueError(f"{what}: HRIRs of {hr.shape[2]} samples are longer than the transform of {nb}: the reference "
+                         "would silently truncate them")
+    Hh = ops.rfft_pow2(hr.reshape(Ls * 2, -1).contiguous(), nb).view(Ls, 2, nb // 2 + 1)
+    return h, Fd, nb, n2, rot.contiguous(), Hh
+
+
+def _binaural_out(out, total: int, dev, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.zeros((total, 2), dtype=torch.float32, device=dev)
+    if (out.dtype != torch.float32 or tuple(out.shape) != (total, 2) or not out.is_contiguous()
+            or out.device != torch.device(dev)):
+        raise ValueError(f"{what}: out must be a contiguous float32 ({total}, 2) matrix on the device")
+    return out.zero_()
+
+
+def binaural_compose_torch(rot, Hh, alpha: float, k0: int, nseg: int, Ah, row_off: int = 0) -> torch.Tensor:
+    """``hip_ops.binaural_compose`` in rows mode in stock tensor operations, the reference's order of operations
+    (interpolate, rotate, contract with the conjugated HRTFs): for more than 16 channels, and the float32 yardstick of the
+    kernel's bound in tests/test_gpu_binaural.py."""
+    k = torch.arange(k0, k0 + nseg, device=rot.device)
+    kp = (k - 1).clamp_(min=0)
+    a = torch.where(k == 0, 1.0, float(alpha)).to(torch.float32)
+    Rw = a.view(-1, 1, 1) * rot[k] + (1.0 - a).view(-1, 1, 1) * rot[kp]
+    Aw = a.view(-1, 1, 1) * Ah[k - row_off] + (1.0 - a).view(-1, 1, 1) * Ah[kp - row_off]
+    rotated = torch.matmul(Rw.to(Aw.dtype), Aw)                                      # (nseg, Ls, Kb)
+    return torch.einsum('nef,knf->kef', Hh.conj(), rotated)
+
+
+def _binaural_run(x, P: int, h: int, Fd: int, nb: int, n2: int, chunk: int, out, compose):
+    """compose -> BRIRs at nb -> their spectra at n2 -> product with the stimulus blocks' -> inverse transform ->
+    overlap-add, ``chunk`` segments at a time.  ``compose(k0, k1)`` returns B (k1 - k0, 2, nb / 2 + 1)."""
+    dev = x.device
+    blocks = x.view(P, h)
+    tails = [torch.empty((Fd, 2), dtype=torch.float32, device=dev) for _ in range(2)]
+    for i, k0 in enumerate(range(0, P, chunk)):
+        k1 = min(k0 + chunk, P)
+        B = compose(k0, k1)
+        brir = ops.irfft_pow2_fwd(B.reshape(-1, B.shape[-1]), nb)                    # circular at nb, as the reference's
+        Z = ops.rfft_pow2(brir, n2).view(k1 - k0, 2, -1) * ops.rfft_pow2(blocks[k0:k1], n2).unsqueeze(1)
+        s = ops.irfft_pow2_fwd(Z.view(2 * (k1 - k0), -1), n2).view(k1 - k0, 2, n2)
+        ops.binaural_ola(s, k0, P, h, nb, Fd, out, tails[i & 1] if k0 else None, tails[1 - (i & 1)])
+    return out
+
+
+@torch.no_grad()
+def render_binaural_moving_listener_bands(nets, z_values, norm_listener_position, taps, length: int, hrir_sh, path,
+                                          rotations, stimulus, update_ms: float = 100.0, alpha: float = 0.5,
+                                          fade_len_ms: Optional[float] = None, sample_rate: Optional[float] = None,
+                                          chunk: int = 32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A dry stimulus heard over headphones by a listener who walks over the receiver grid and turns their head, from the
+    trained directional bands in one pass: the reference's ``binaural_dynamic_rendering.binaural_filter_overlap_add``
+    (sound_examples.py:356-535) on the ambisonic RIRs ``infer_directional_bands(.., directional=False, rows=path)``, one
+    row and one head orientation per update interval.  With Ls = (order + 1)^2, L the RIRs' length:
+
+        nb = 2^ceil(log2 L),  Kb = nb / 2 + 1;   A_k = rfft(a[path[k]], nb),  Hh = rfft(hrir_sh, nb)              (:408-422)
+        h = int(update_ms 1e-3 fs),  Fd = int(fade_len_ms 1e-3 fs) (default: = h),  total = P h          (utils.py:62-80; :478)
+        x = the stimulus as float32, repeated or cut to total;  x_k = x[k h : (k + 1) h]                          (:149-161)
+        Rw_0 = R_0,  Rw_k = alpha R_k + (1 - alpha) R_{k-1};   Aw_0 = A_0,  Aw_k = alpha A_k + (1 - alpha) A_{k-1}  (:450-461)
+        B_k[e][f] = sum_n conj(Hh[n][e][f]) sum_m Rw_k[n][m] Aw_k[m][f];   b_k[e] = irfft(B_k[e], nb)             (:463-469)
+        s_k[e] = fftconvolve(x_k, b_k[e], 'full')[: min(h + nb - 1, total - k h)]                                 (:503-511)
+        out[k h + i][e] += s_k[e][i];  for k >= 1 and i < Fd instead  t_{k-1}[e][i] fade_out[i] + s_k[e][i] fade_in[i]
+        fade_in = sqrt(0.5 (1 + linspace(-1, 1, Fd))),  fade_out = sqrt(0.5 (1 - linspace(-1, 1, Fd))),
+        t_{k-1}[e] = the LAST Fd samples of the cut s_{k-1}[e]                                    (:118-127, :480-485, :527-533)
+
+    The reference's quirks are kept: NO recursion -- the interpolation takes the RAW previous position and orientation
+    (the omnidirectional ``render_moving_listener_bank`` recurses on the filter); the HRTFs enter CONJUGATED and the BRIR is
+    a CIRCULAR product at nb; the reference indexes its RIR store by the segment number, its dataset being the path in
+    order: here ``path`` selects the rows, a_k = a[path[k]].  The receiver enters the directional render only through its
+    SH weights, so with C the Q G Ls band signals and W the weights of ``infer_directional_bands``
+
+        B_k[e][f] = sum_n conj(Hh[n][e][f]) sum_m Rw_k[n][m] sum_s Wk_k[s][m] rfft(C, nb)[s Ls + m][f]
+
+    (csrc/binaural.hip): the path's ambisonic RIRs and their spectra never exist.  The BRIRs are the exception: circular at
+    nb, convolved at n2 = the power of two >= h + nb - 1, a chunk's BRIRs (chunk x 2 x nb floats) pass through memory once
+    between the two transforms.  The product with the stimulus blocks' spectra is stock complex multiplication.
+
+    ``nets``, ``z_values``, ``norm_listener_position``, ``taps``, ``length``: as ``infer_directional_bands``.  ``hrir_sh``
+    (Ls, 2, Mh): the HRIRs in the SH domain, a DECLARED INPUT (the reference reads a SOFA file and calls
+    ``get_spherical_harmonic_representation(order)``); Mh <= nb, a longer set is a ValueError (the reference would silently
+    truncate it).  ``rotations`` (P, Ls, Ls): the real SH rotation matrices, a DECLARED INPUT -- the convention is the
+    reference's call ``spaudiopy.sph.sh_rotation_matrix(order, -yaw, +el, 0, 'real')`` per position, after its own sign
+    flip of the elevation (:388, :444-449).  ``path``: P rows of ``norm_listener_position``, repeats and any order allowed;
+    ``stimulus``: 1-D, tensor or numpy; ``sample_rate`` defaults to the nets'; ``out``: a contiguous float32 (P h, 2) buffer.
+    Scope: P >= 1, h >= 1, 1 <= Fd <= h, 0 <= alpha <= 1, P h < 2^31, L >= 9.  Every call starts fresh: the ``prev_*`` state
+    that the reference leaves on its object is not reproduced; the reference's constructor always takes ``late_rirs``, here
+    the RIRs are the bands' (pass others to ``render_binaural_moving_listener``).  More than 32 band signals per channel
+    or 16 channels: the rows are rendered with ``infer_directional_bands`` and go through
+    ``render_binaural_moving_listener``.  Not covered: a SOFA reader, building rotation matrices from angles, loudness
+    normalisation, the animation, wav export.
+    Returns (P h, 2) float32, ears interleaved as the reference returns them."""
+    what = "render_binaural_moving_listener_bands"
+    nets = list(nets)
+    if path is None or torch.as_tensor(path).numel() == 0:
+        raise ValueError(f"{what}: an empty path")
+    if not nets:
+        raise ValueError(f"{what}: no bands")
+    fs = float(getattr(nets[0], "sample_rate") if sample_rate is None else sample_rate)
+    G, Ls = nets[0].num_groups, nets[0].num_delay_lines_per_group
+    if len(nets) * G > ops.BINAURAL_MAX_S or Ls > ops.BINAURAL_MAX_LS:
+        y = infer_directional_bands(nets, z_values, norm_listener_position, taps, length, directional=False, rows=path)
+        return render_binaural_moving_listener(y, hrir_sh, None, rotations, stimulus, fs, update_ms, alpha, fade_len_ms,
+                                               chunk, out)
+    dev = nets[0].output_gains.device
+    P = torch.as_tensor(path).numel()
+    L = max(1, min(int(length), 2 * (z_values.shape[-1] - 1)))
+    h, Fd, nb, n2, rot, Hh = _binaural_plan(P, L, fs, update_ms, alpha, fade_len_ms, rotations, hrir_sh, Ls, dev, what)
+    x = _moving_stimulus(stimulus, P * h, dev, what)
+    W, C, _, _ = _directional_inputs(nets, z_values, norm_listener_position, taps, length, path, 4096, what)
+    out = _binaural_out(out, P * h, dev, what)
+    Ch = ops.rfft_pow2(C, nb)
+    return _binaural_run(x, P, h, Fd, nb, n2, int(chunk), out,
+                         lambda k0, k1: ops.binaural_compose(rot, Hh, float(alpha), k0, k1 - k0, W=W, Ch=Ch))
+
+
+@torch.no_grad()
+def render_binaural_moving_listener(ambi_rirs, hrir_sh, path, rotations, stimulus, fs: float, update_ms: float = 100.0,
+                                    alpha: float = 0.5, fade_len_ms: Optional[float] = None, chunk: int = 32,
+                                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The render of ``render_binaural_moving_listener_bands`` for ANY ambisonic RIRs (for instance a measured dataset's, or
+    its late parts, which the reference's constructor always takes): ``ambi_rirs`` (R, Ls, L) tensor or numpy, ``path``: P
+    of its rows (None: every row in order), ``hrir_sh`` (Ls, 2, Mh), ``rotations`` (P, Ls, Ls), ``stimulus`` 1-D, ``fs`` the
+    sample rate.  The rows' spectra DO pass through memory here, ``chunk`` segments at a time (the general path, not the
+    bands'), into the same kernels in rows mode; more than 16 channels: the composition in stock tensor operations
+    (``binaural_compose_torch``).  The same quirks and scope.
+    Returns (P h, 2) float32 on the device of ``ambi_rirs`` (a host array: on the current device)."""
+    what = "render_binaural_moving_listener"
+    rirs = torch.as_tensor(ambi_rirs)
+    if rirs.dim() != 3 or rirs.shape[1] < 1 or rirs.shape[2] < 1:
+        raise ValueError(f"{what}: ambi_rirs (R, Ls, L)")
+    dev = rirs.device if rirs.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if path is None:
+        sel = torch.arange(rirs.shape[0])
+        if sel.numel() == 0:
+            raise ValueError(f"{what}: an empty path")
+    else:
+        if torch.as_tensor(path).numel() == 0:
+            raise ValueError(f"{what}: an empty path")
+        sel = _edc_rows(path, rirs.shape[0], torch.device("cpu"), what)
+    sel = sel.to(rirs.device)
+    P, Ls, L = sel.numel(), int(rirs.shape[1]), int(rirs.shape[2])
+    h, Fd, nb, n2, rot, Hh = _binaural_plan(P, L, float(fs), update_ms, alpha, fade_len_ms, rotations, hrir_sh, Ls, dev, what)
+    x = _moving_stimulus(stimulus, P * h, dev, what)
+    out = _binaural_out(out, P * h, dev, what)
+
+    def compose(k0, k1):
+        lo = max(k0 - 1, 0)                                                          # (the raw previous position)
+        r = rirs[sel[lo:k1]].to(device=dev, dtype=torch.float32).reshape(-1, L)
+        Ah = ops.rfft_pow2(r, nb).view(k1 - lo, Ls, -1)
+        if Ls > ops.BINAURAL_MAX_LS:
+            return binaural_compose_torch(rot, Hh, float(alpha), k0, k1 - k0, Ah, lo).contiguous()
+        return ops.binaural_compose(rot, Hh, float(alpha), k0, k1 - k0, Ah=Ah, row_off=lo)
+    return _binaural_run(x, P, h, Fd, nb, n2, int(chunk), out, compose)
 
 
 def sum_bands(local_band_rirs: Sequence[torch.Tensor], group=None, dst: int = 0, device=None) -> Optional[torch.Tensor]:

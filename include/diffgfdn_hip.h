@@ -1120,6 +1120,36 @@ int gfdn_moving_ola(const float* s, int ld_s, int nseg, int k0, int P, int h, in
 int gfdn_dir_render(const float* w, const float* c, int ld_c, const float* a, int R, int S, int Ls, int J, int n, float* out,
                     int ld_out, void* stream);
 
+/* ---- a moving, head-turning listener heard binaurally  (sound_examples.py:356-535 ``binaural_dynamic_rendering``: per update
+ * interval the position's ambisonic spectrum and the head's SH rotation matrix, each interpolated with the RAW previous one
+ * (no recursion), the conjugated SH-domain HRTFs, the BRIR as a circular product at nb = 2^ceil(log2 L); fftconvolve per ear;
+ * overlap-add with square-root cross-fades) in two launches (csrc/binaural.hip).  Kb = nb / 2 + 1; spectra complex64,
+ * pitches in complex elements.
+ *   gfdn_binaural_compose: for the segments k = k0 .. k0 + nseg - 1 of a path of P, per bin f < Kb and ear e:
+ *         row_k = (path ? path[k] : k) - row_off
+ *         a_k[m] = sum_{s < S} w[(row_k S + s) Ls + m] ch[(s Ls + m) ld_c + f]                      (bank mode, S > 0)
+ *                = ah[(row_k Ls + m) ld_a + f]                                      (rows mode: S = 0, w = ch = NULL)
+ *         g_k[m][e] = sum_{n < Ls} rot[(k Ls + n) Ls + m] conj(hh[(2 n + e) ld_h + f])
+ *         b[((k - k0) 2 + e) ld_b + f] = sum_{m < Ls} gw[m][e] aw[m],    aw = alpha a_k + (1 - alpha) a_{k-1} and
+ *         gw = alpha g_k + (1 - alpha) g_{k-1} for k >= 1, the raw values at k = 0.
+ *     rot (P, Ls, Ls) and path (P or NULL) are WHOLE-PATH arrays: segment k0 - 1 is read, there is no state buffer and a path
+ *     in chunks gives the bits of one launch.  nrows: the rows of w (bank) or ah (rows mode); without path the rows
+ *     k0 - 1 - row_off .. k0 + nseg - 1 - row_off must lie inside, the values of path are the caller's to check.
+ *     0 <= alpha <= 1; S <= 32 and Ls <= 16 (GFDN_E_UNSUPPORTED above); spectra 8-byte aligned; nothing is read or written
+ *     behind bin Kb - 1 of a row.
+ *   gfdn_binaural_ola: s (nseg 2, ld_s >= h + nb - 1), row (k - k0) 2 + e the time-domain segment k of ear e; segment k covers
+ *     out[k h .. k h + len_k), len_k = min(h + nb - 1, P h - k h); out (P h, 2) float32 interleaved, zeroed by the caller
+ *     before the first chunk.  Every covered sample takes one running sum from its value on, k ascending:
+ *         i >= Fd or k == 0:  + s_k[i]     else:  + t_{k-1}[i] sqrt((Fd - 1 - i) / (Fd - 1)) + s_k[i] sqrt(i / (Fd - 1))
+ *     (Fd = 1: t).  t_{k-1} = the last Fd samples of the cut segment k - 1: rows of s, or tail_in (Fd, 2) for k = k0 > 0;
+ *     tail_out (Fd, 2) receives the tail of segment k0 + nseg - 1 and must not be tail_in.  Gather form, no atomics: chunks
+ *     give the bits of one launch.  1 <= Fd <= h, P h < 2^31; out and the tails 8-byte aligned. */
+int gfdn_binaural_compose(const float* w, const float* ch_c64, int ld_c, int S, const float* ah_c64, int ld_a,
+                          const long long* path, int row_off, int nrows, const float* rot, const float* hh_c64, int ld_h,
+                          int P, int k0, int nseg, int Kb, int Ls, float alpha, float* b_c64, int ld_b, void* stream);
+int gfdn_binaural_ola(const float* s, int ld_s, int nseg, int k0, int P, int h, int nb, int Fd, const float* tail_in,
+                      float* tail_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

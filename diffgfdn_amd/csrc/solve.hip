@@ -1266,6 +1266,52 @@ static int check_solve_args(const double* turns, int K, int nblk, int nper, cons
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Which kernel a shape runs: the ONE rule both launchers (and gfdn_solve_path) switch on.  Family = GFDN_PATH_*
+// of the header, GFDN_PATH_PRECISE added for the float64 instantiations; negative: the launcher's error.
+//   precise                         -> the lane-parallel template <np, double2> (no shortcut of any kind)
+//   n <= 4, nblk <= S4_MAXBLK       -> thread-per-system k_solve4_*
+//   n <= 8, nblk <= S8_MAXBLK       -> thread-per-system k_solve8_* (the backward only with the saved solution)
+//   n = 9 / 10 .. 12                -> three rows per lane (k_solve_*_rl<9>) / packed lane groups (k_solve_*_pk<n>)
+//   everything else                 -> the lane-parallel template <np>, np = 4, 8, 16, 32
+// ------------------------------------------------------------------------------------------
+static int generic_path(int np) {
+  switch (np) {
+    case 4: return GFDN_PATH_GENERIC4;
+    case 8: return GFDN_PATH_GENERIC8;
+    case 16: return GFDN_PATH_GENERIC16;
+    default: return GFDN_PATH_GENERIC32;
+  }
+}
+static int solve_path(int nblk, int nper, bool precise, bool have_Y, bool backward) {
+  if (nblk <= 0 || nper <= 0) return GFDN_E_BADARG;
+  if (nper > GFDN_MAX_BLOCK) return GFDN_E_UNSUPPORTED;
+  const int np = pick_np(nper);
+  if (precise) return generic_path(np) | GFDN_PATH_PRECISE;
+  if (np == 4 && nblk <= S4_MAXBLK) return GFDN_PATH_SOLVE4;
+  if (np == 8 && nblk <= S8_MAXBLK && (!backward || have_Y)) return GFDN_PATH_SOLVE8;   // (needs the saved solution)
+  switch (nper) {
+    case 9: return GFDN_PATH_RL9;
+    case 10: return GFDN_PATH_PK10;
+    case 11: return GFDN_PATH_PK11;
+    case 12: return GFDN_PATH_PK12;
+    default: return generic_path(np);
+  }
+}
+// bins per workgroup of a path's lane-parallel kernel (the thread-per-system launches are sized by work items instead)
+static int solve_path_spb(int path, int nper) {
+  switch (path & ~GFDN_PATH_PRECISE) {
+    case GFDN_PATH_RL9: return 4 * (64 / ((9 + RL_R - 1) / RL_R));        // three rows per lane
+    case GFDN_PATH_PK10: return 4 * (64 / 10);
+    case GFDN_PATH_PK11: return 4 * (64 / 11);
+    case GFDN_PATH_PK12: return 4 * (64 / 12);
+    default: return 256 / pick_np(nper);
+  }
+}
+extern "C" int gfdn_solve_path(int nblk, int nper, int precise, int have_Y, int backward) {
+  return solve_path(nblk, nper, precise != 0, have_Y != 0, backward != 0);
+}
+
 static int solve_fwd_run(const double* turns, const double* logr, int K, int nblk, int nper,
                          const float* A, const float* delays, const float* inv_gamma,
                          const float* b, int transpose, float* Y, void* stream, const float2* g_igz,
@@ -1275,48 +1321,28 @@ static int solve_fwd_run(const double* turns, const double* logr, int K, int nbl
   if (rc) return rc;
   if (!Y) return GFDN_E_BADARG;
   SolveArgs a{turns, logr, K, nblk, nper, A, delays, inv_gamma, b, transpose, g_igz, ig64};
-  const int np = pick_np(nper);
-  const int pk = (!precise && nper >= 9 && nper <= 12) ? nper : 0;       // three rows per lane (k_solve_fwd_rl)
-  const int spb = pk == 9 ? 4 * (64 / ((pk + RL_R - 1) / RL_R)) : (pk ? 4 * (64 / pk) : 256 / np);
+  const int path = solve_path(nblk, nper, precise, true, false);
+  if (path < 0) return path;
+  const int spb = solve_path_spb(path, nper);
   dim3 grid((K + spb - 1) / spb, nblk), block(256);
+  const dim3 items_grid((unsigned)(((long long)K * nblk + 255) / 256));      // thread-per-system: one work item per thread
   hipStream_t s = (hipStream_t)stream;
-  if (pk) {
-    switch (pk) {
-      case 9: hipLaunchKernelGGL(k_solve_fwd_rl<9>, grid, block, 0, s, a, (float2*)Y); break;
-      case 10: hipLaunchKernelGGL(k_solve_fwd_pk<10>, grid, block, 0, s, a, (float2*)Y); break;
-      case 11: hipLaunchKernelGGL(k_solve_fwd_pk<11>, grid, block, 0, s, a, (float2*)Y); break;
-      default: hipLaunchKernelGGL(k_solve_fwd_pk<12>, grid, block, 0, s, a, (float2*)Y); break;
-    }
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (precise) {
-    switch (np) {
-      case 4: hipLaunchKernelGGL((k_solve_fwd<4, double2>), grid, block, 0, s, a, (float2*)Y); break;
-      case 8: hipLaunchKernelGGL((k_solve_fwd<8, double2>), grid, block, 0, s, a, (float2*)Y); break;
-      case 16: hipLaunchKernelGGL((k_solve_fwd<16, double2>), grid, block, 0, s, a, (float2*)Y); break;
-      default: hipLaunchKernelGGL((k_solve_fwd<32, double2>), grid, block, 0, s, a, (float2*)Y); break;
-    }
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (np == 4 && nblk <= S4_MAXBLK) {
-    const long long items = (long long)K * nblk;
-    hipLaunchKernelGGL(k_solve4_fwd, dim3((unsigned)((items + 255) / 256)), block, 0, s, a, (float2*)Y);
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (np == 8 && nblk <= S8_MAXBLK) {
-    const long long items = (long long)K * nblk;
-    hipLaunchKernelGGL(k_solve8_fwd, dim3((unsigned)((items + 255) / 256)), block, 0, s, a, (float2*)Y);
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (np) {
-    case 4: hipLaunchKernelGGL(k_solve_fwd<4>, grid, block, 0, s, a, (float2*)Y); break;
-    case 8: hipLaunchKernelGGL(k_solve_fwd<8>, grid, block, 0, s, a, (float2*)Y); break;
-    case 16: hipLaunchKernelGGL(k_solve_fwd<16>, grid, block, 0, s, a, (float2*)Y); break;
-    default: hipLaunchKernelGGL(k_solve_fwd<32>, grid, block, 0, s, a, (float2*)Y); break;
+  switch (path) {
+    case GFDN_PATH_SOLVE4: hipLaunchKernelGGL(k_solve4_fwd, items_grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_SOLVE8: hipLaunchKernelGGL(k_solve8_fwd, items_grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_RL9: hipLaunchKernelGGL(k_solve_fwd_rl<9>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_PK10: hipLaunchKernelGGL(k_solve_fwd_pk<10>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_PK11: hipLaunchKernelGGL(k_solve_fwd_pk<11>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_PK12: hipLaunchKernelGGL(k_solve_fwd_pk<12>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC4: hipLaunchKernelGGL(k_solve_fwd<4>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC8: hipLaunchKernelGGL(k_solve_fwd<8>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC16: hipLaunchKernelGGL(k_solve_fwd<16>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC32: hipLaunchKernelGGL(k_solve_fwd<32>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC4 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_fwd<4, double2>), grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC8 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_fwd<8, double2>), grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC16 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_fwd<16, double2>), grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC32 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_fwd<32, double2>), grid, block, 0, s, a, (float2*)Y); break;
+    default: return GFDN_E_UNSUPPORTED;      // (no such path: solve_path and this switch must list the same values)
   }
   GFDN_LAUNCH_CHECK();
   return 0;
@@ -1392,61 +1418,45 @@ static int solve_bwd_run(const double* turns, const double* logr, int K, int nbl
   if (rc) return rc;
   if (!gY || !gA || !gb || !ginv_gamma || !work) return GFDN_E_BADARG;
   SolveArgs a{turns, logr, K, nblk, nper, A, delays, inv_gamma, b, transpose, g_igz, ig64};
-  const int np = pick_np(nper);
-  const int pk = (!precise && nper >= 9 && nper <= 12) ? nper : 0;       // three rows per lane (k_solve_bwd_rl)
-  const int spb = pk == 9 ? 4 * (64 / ((pk + RL_R - 1) / RL_R)) : (pk ? 4 * (64 / pk) : 256 / np);
+  const int path = solve_path(nblk, nper, precise, Y != nullptr, true);
+  if (path < 0) return path;
+  const int spb = solve_path_spb(path, nper);
   int nparts = (K + spb - 1) / spb;
   if (nparts > GFDN_PARTIAL_BLOCKS) nparts = GFDN_PARTIAL_BLOCKS;
-  const bool lin = !precise && np == 4 && nblk <= S4_MAXBLK;
-  const bool lin8 = !precise && np == 8 && nblk <= S8_MAXBLK && Y != nullptr;   // (needs the saved solution)
-  if (lin || lin8) nparts = solve4_parts(K, nblk);
+  if (path == GFDN_PATH_SOLVE4 || path == GFDN_PATH_SOLVE8) nparts = solve4_parts(K, nblk);
   dim3 grid(nparts, nblk), block(256);
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)work;
-  if (lin) {
-    const int items = solve4_items(nblk);
-    hipLaunchKernelGGL(k_solve4_bwd, dim3(nparts), block, (size_t)items * 25 * sizeof(float), s, a,
-                       (const float2*)gY, (const float2*)Y, partial, items);
-    GFDN_LAUNCH_CHECK();
-    const int tot4 = nblk * (nper * nper + 2 * nper);
-    hipLaunchKernelGGL(k_solve_bwd_finish, dim3(tot4), dim3(256), 0, s, partial, nparts, nblk, nper, gA, gb, ginv_gamma);
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (lin8) {
-    const size_t lds8 = (size_t)80 * S8_BWD_T * sizeof(float);
-    if ((rc = ensure_dyn_lds(k_solve8_bwd, lds8))) return rc;
-    hipLaunchKernelGGL(k_solve8_bwd, dim3(nparts), dim3(S8_BWD_T), lds8, s, a, (const float2*)gY,
-                       (const float2*)Y, partial, (S8_BWD_T / nblk) * nblk);
-    GFDN_LAUNCH_CHECK();
-    const int tot8 = nblk * (nper * nper + 2 * nper);
-    hipLaunchKernelGGL(k_solve_bwd_finish, dim3(tot8), dim3(256), 0, s, partial, nparts, nblk, nper, gA, gb, ginv_gamma);
-    GFDN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (pk) {
-    switch (pk) {
-      case 9:
-        if (Y) hipLaunchKernelGGL((k_solve_bwd_rl<9, true>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial);
-        else hipLaunchKernelGGL((k_solve_bwd_rl<9, false>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial);
-        break;
-      case 10: hipLaunchKernelGGL(k_solve_bwd_pk<10>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-      case 11: hipLaunchKernelGGL(k_solve_bwd_pk<11>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-      default: hipLaunchKernelGGL(k_solve_bwd_pk<12>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
+  const float2* gY2 = (const float2*)gY;
+  const float2* Y2 = (const float2*)Y;
+  switch (path) {
+    case GFDN_PATH_SOLVE4: {
+      const int items = solve4_items(nblk);
+      hipLaunchKernelGGL(k_solve4_bwd, dim3(nparts), block, (size_t)items * 25 * sizeof(float), s, a, gY2, Y2, partial, items);
+      break;
     }
-  } else if (precise) {
-    switch (np) {
-      case 4: hipLaunchKernelGGL((k_solve_bwd<4, double2>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-      case 8: hipLaunchKernelGGL((k_solve_bwd<8, double2>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-      case 16: hipLaunchKernelGGL((k_solve_bwd<16, double2>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-      default: hipLaunchKernelGGL((k_solve_bwd<32, double2>), grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
+    case GFDN_PATH_SOLVE8: {
+      const size_t lds8 = (size_t)80 * S8_BWD_T * sizeof(float);
+      if ((rc = ensure_dyn_lds(k_solve8_bwd, lds8))) return rc;
+      hipLaunchKernelGGL(k_solve8_bwd, dim3(nparts), dim3(S8_BWD_T), lds8, s, a, gY2, Y2, partial, (S8_BWD_T / nblk) * nblk);
+      break;
     }
-  } else
-  switch (np) {
-    case 4: hipLaunchKernelGGL(k_solve_bwd<4>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-    case 8: hipLaunchKernelGGL(k_solve_bwd<8>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-    case 16: hipLaunchKernelGGL(k_solve_bwd<16>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
-    default: hipLaunchKernelGGL(k_solve_bwd<32>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial); break;
+    case GFDN_PATH_RL9:
+      if (Y) hipLaunchKernelGGL((k_solve_bwd_rl<9, true>), grid, block, 0, s, a, gY2, Y2, partial);
+      else hipLaunchKernelGGL((k_solve_bwd_rl<9, false>), grid, block, 0, s, a, gY2, Y2, partial);
+      break;
+    case GFDN_PATH_PK10: hipLaunchKernelGGL(k_solve_bwd_pk<10>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_PK11: hipLaunchKernelGGL(k_solve_bwd_pk<11>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_PK12: hipLaunchKernelGGL(k_solve_bwd_pk<12>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC4: hipLaunchKernelGGL(k_solve_bwd<4>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC8: hipLaunchKernelGGL(k_solve_bwd<8>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC16: hipLaunchKernelGGL(k_solve_bwd<16>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC32: hipLaunchKernelGGL(k_solve_bwd<32>, grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC4 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_bwd<4, double2>), grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC8 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_bwd<8, double2>), grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC16 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_bwd<16, double2>), grid, block, 0, s, a, gY2, Y2, partial); break;
+    case GFDN_PATH_GENERIC32 | GFDN_PATH_PRECISE: hipLaunchKernelGGL((k_solve_bwd<32, double2>), grid, block, 0, s, a, gY2, Y2, partial); break;
+    default: return GFDN_E_UNSUPPORTED;      // (no such path: solve_path and this switch must list the same values)
   }
   GFDN_LAUNCH_CHECK();
   const int tot = nblk * (nper * nper + 2 * nper);
@@ -1614,11 +1624,20 @@ __global__ __launch_bounds__(256) void k_solve_phi_bwd(PhiArgs a, const float2* 
   }
 }
 
+// The dense N x N system of a bin runs on the lane-parallel template of pick_np(N) lanes, N = G nper: one rule for both
+// launchers and gfdn_solve_phi_path (GFDN_PATH_GENERIC*; negative: the launcher's error)
+static int solve_phi_path(int G, int nper) {
+  if (G <= 0 || nper <= 0) return GFDN_E_BADARG;
+  if (G > GFDN_MAX_GROUPS || G * nper > GFDN_MAX_BLOCK) return GFDN_E_UNSUPPORTED;
+  return generic_path(pick_np(G * nper));
+}
+extern "C" int gfdn_solve_phi_path(int G, int nper) { return solve_phi_path(G, nper); }
+
 static int phi_args_ok(const double* turns, int K, int G, int nper, const float* BM, const float* Phi,
                        const float* delays, const float* ig, const float* b) {
   if (!turns || !BM || !Phi || !delays || !ig || !b || K <= 0 || G <= 0 || nper <= 0) return GFDN_E_BADARG;
-  if (G > GFDN_MAX_GROUPS || G * nper > GFDN_MAX_BLOCK) return GFDN_E_UNSUPPORTED;
-  return 0;
+  const int path = solve_phi_path(G, nper);
+  return path < 0 ? path : 0;
 }
 
 extern "C" int gfdn_solve_phi_absorb_fwd(const double* turns, const double* logr, int K, int G, int nper,
@@ -1630,14 +1649,15 @@ extern "C" int gfdn_solve_phi_absorb_fwd(const double* turns, const double* logr
   if (!Y) return GFDN_E_BADARG;
   PhiArgs a{turns, logr, K, G * nper, nper, BM, (const float2*)Phi_c64, delays, inv_gamma, b,
             (const float2*)inv_gamma_bins_c64};
-  const int np = pick_np(G * nper), spb = 256 / np;
+  const int path = solve_phi_path(G, nper), spb = 256 / pick_np(G * nper);
   dim3 grid((K + spb - 1) / spb), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (np) {
-    case 4: hipLaunchKernelGGL(k_solve_phi_fwd<4>, grid, block, 0, s, a, (float2*)Y); break;
-    case 8: hipLaunchKernelGGL(k_solve_phi_fwd<8>, grid, block, 0, s, a, (float2*)Y); break;
-    case 16: hipLaunchKernelGGL(k_solve_phi_fwd<16>, grid, block, 0, s, a, (float2*)Y); break;
-    default: hipLaunchKernelGGL(k_solve_phi_fwd<32>, grid, block, 0, s, a, (float2*)Y); break;
+  switch (path) {
+    case GFDN_PATH_GENERIC4: hipLaunchKernelGGL(k_solve_phi_fwd<4>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC8: hipLaunchKernelGGL(k_solve_phi_fwd<8>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC16: hipLaunchKernelGGL(k_solve_phi_fwd<16>, grid, block, 0, s, a, (float2*)Y); break;
+    case GFDN_PATH_GENERIC32: hipLaunchKernelGGL(k_solve_phi_fwd<32>, grid, block, 0, s, a, (float2*)Y); break;
+    default: return GFDN_E_UNSUPPORTED;      // (a path without a kernel is an error, never a silent return of 0)
   }
   GFDN_LAUNCH_CHECK();
   return 0;
@@ -1665,17 +1685,18 @@ extern "C" int gfdn_solve_phi_absorb_bwd(const double* turns, const double* logr
   const int N = G * nper;
   PhiArgs a{turns, logr, K, N, nper, BM, (const float2*)Phi_c64, delays, inv_gamma, b,
             (const float2*)inv_gamma_bins_c64};
-  const int np = pick_np(N), spb = 256 / np;
+  const int path = solve_phi_path(G, nper), spb = 256 / pick_np(N);
   int nparts = (K + spb - 1) / spb;
   if (nparts > GFDN_PARTIAL_BLOCKS) nparts = GFDN_PARTIAL_BLOCKS;
   dim3 grid(nparts), block(256);
   hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)work;
-  switch (np) {
-    case 4: hipLaunchKernelGGL(k_solve_phi_bwd<4>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
-    case 8: hipLaunchKernelGGL(k_solve_phi_bwd<8>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
-    case 16: hipLaunchKernelGGL(k_solve_phi_bwd<16>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
-    default: hipLaunchKernelGGL(k_solve_phi_bwd<32>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
+  switch (path) {
+    case GFDN_PATH_GENERIC4: hipLaunchKernelGGL(k_solve_phi_bwd<4>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
+    case GFDN_PATH_GENERIC8: hipLaunchKernelGGL(k_solve_phi_bwd<8>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
+    case GFDN_PATH_GENERIC16: hipLaunchKernelGGL(k_solve_phi_bwd<16>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
+    case GFDN_PATH_GENERIC32: hipLaunchKernelGGL(k_solve_phi_bwd<32>, grid, block, 0, s, a, (const float2*)gY, (const float2*)Y, partial, (float2*)gPhi_c64); break;
+    default: return GFDN_E_UNSUPPORTED;      // (a path without a kernel is an error, never a silent return of 0)
   }
   GFDN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_solve_bwd_finish, dim3(N * N + 2 * N), dim3(256), 0, s, partial, nparts, 1, N, gBM, gb, ginv_gamma);

@@ -185,6 +185,30 @@ def solve_bwd(turns, logr, A, delays, inv_gamma, b, gY, transpose=False, Y=None,
     return gA, gb, gig
 
 
+# kernel families of the solve launchers (GFDN_PATH_* of include/diffgfdn_hip.h)
+SOLVE_PATHS = {1: "solve4", 2: "solve8", 3: "rl9", 4: "pk10", 5: "pk11", 6: "pk12", 7: "generic4", 8: "generic8",
+               9: "generic16", 10: "generic32"}
+_PATH_PRECISE = 16
+
+
+def _path_name(code: int, what: str) -> Tuple[str, bool]:
+    if code < 0:
+        _lib.check(code, what)
+    return SOLVE_PATHS[code & ~_PATH_PRECISE], bool(code & _PATH_PRECISE)
+
+
+def solve_path(nblk: int, nper: int, precise: bool = False, have_Y: bool = False, backward: bool = False) -> Tuple[str, bool]:
+    """(family, float64?) of the kernel that ``solve_fwd`` / ``solve_bwd`` launch for this shape -- the rule the launchers
+    themselves switch on; raises as they would for sizes they refuse.  A host-side query: needs no GPU."""
+    return _path_name(_lib.load().gfdn_solve_path(int(nblk), int(nper), int(precise), int(have_Y), int(backward)),
+                      "gfdn_solve_path")
+
+
+def solve_phi_path(G: int, nper: int) -> Tuple[str, bool]:
+    """The same for ``solve_phi_fwd`` / ``solve_phi_bwd`` (one dense system of N = G nper lines per bin)."""
+    return _path_name(_lib.load().gfdn_solve_phi_path(int(G), int(nper)), "gfdn_solve_phi_path")
+
+
 def solve_phi_fwd(turns, logr, BM, Phi, nper, delays, inv_gamma, b, inv_gamma_bins=None) -> torch.Tensor:
     """FILTER coupling: A(z_k) = BM o kron(Phi_k, 1).  BM (N, N) f32, Phi (K, G, G) complex64 -> Y (K, N).
     ``inv_gamma_bins`` (K, N) complex64: 1 / Gamma_i(z_k) of absorption filters on the lines (multiplies inv_gamma)."""

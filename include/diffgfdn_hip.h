@@ -152,6 +152,28 @@ int gfdn_solve_phi_absorb_bwd(const double* turns, const double* logr, int K, in
                               const float* Y_c64, float* gBM, float* gb, float* ginv_gamma, float* gPhi_c64,
                               void* work, void* stream);
 
+/* Which kernel family the solve entry points above launch for a shape (host-side query, nothing is launched): one of
+ * GFDN_PATH_*, with GFDN_PATH_PRECISE added for the float64 instantiations of the precise entry points, or the
+ * negative GFDN_E_* code the launcher would return for these sizes.  have_Y: the backward is handed the saved forward
+ * solution (read only when backward != 0).  The launchers switch on the same function.
+ *   SOLVE4 / SOLVE8: one thread per system (nper <= 4, nblk <= 64 / nper <= 8, nblk <= 32; the backward of SOLVE8 only
+ *   with the saved solution);  RL9: three rows per lane;  PK10 .. PK12: packed lane groups of nper lanes;
+ *   GENERIC4 .. GENERIC32: lane-parallel Gauss-Jordan on 4 .. 32 lanes per system.
+ * The filter-coupled launchers take GENERIC* by N = G nper.                                                              */
+#define GFDN_PATH_SOLVE4 1
+#define GFDN_PATH_SOLVE8 2
+#define GFDN_PATH_RL9 3
+#define GFDN_PATH_PK10 4
+#define GFDN_PATH_PK11 5
+#define GFDN_PATH_PK12 6
+#define GFDN_PATH_GENERIC4 7
+#define GFDN_PATH_GENERIC8 8
+#define GFDN_PATH_GENERIC16 9
+#define GFDN_PATH_GENERIC32 10
+#define GFDN_PATH_PRECISE 16
+int gfdn_solve_path(int nblk, int nper, int precise, int have_Y, int backward);
+int gfdn_solve_phi_path(int G, int nper);
+
 /* ---- second-order-section cascades: SVF output filters  (gain_filters.py:221-241 SOSFilter.forward, :262-402
  * SVF_from_MLP, model.py:588-619) -------------------------------------------------------------------------
  * coef (R, S, 6) float32 = b0 b1 b2 a0 a1 a2 per section (S <= 12), z (K) complex128.  Sections are evaluated in
